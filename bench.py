@@ -21,7 +21,21 @@ and --box 4096,4096,512 run one rank's slab of those configs.  value = cycles/s 
 ghost-0 coarse levels), with the CPU port timed over the same cycles (1 thread and OpenMP) beside the GPU.
 --restriction full_weighting: the build's full-weighting option instead of the 2^d cell average.
 
-At every N the default (weak) run adds the north-star workloads to the same JSON line (`north_star_lines`):
+A plain run (no --full) does what the headline figure needs and no more: it creates the context, ramps the clocks
+(the copy probe's load), runs the warmup cycles, times the K cycles, writes --dump-outputs if asked, and prints the
+line (metric, value, unit, ms_per_step, dtype, config, final_err, hbm_used_GB_rank0).  Everything below is measured
+only with --full: the copy probe's bandwidth figure, the event-timed second pass of the K cycles behind the
+roofline / level0_kernels / finest_smoother_GBps fields, relative_residual, cpu_baseline, the fp64 line and the
+north-star lines.
+
+--dump-outputs DIR: after the timed cycles, what their caller received from them is written to DIR as .npy: `err`
+(float64, the K per-cycle errs ctx.cycles(K) returned) and `psi` (the context's real type: the finest-level
+solution after the last timed cycle, ctx.get_psi(); above DUMP_SAMPLE values, the values at a fixed seeded
+sample of DUMP_SAMPLE flat indices, in ascending index order).  With N ranks each rank writes `err_rank<r>`
+and `psi_rank<r>` of its own slab.  The point-charge input is the same in every run of the same arguments.
+
+With --full, at every N the default (weak) run adds the north-star workloads to the same JSON line
+(`north_star_lines`):
 BASELINE configs[3] (2048^3 V-cycle) and configs[4] (4096^3 F-cycle) as one box split into N z-slabs (N = 1: the
 whole box on one GPU), each run after the previous context is closed, with per-rank halo-exchange and collective
 time from HIP events, so that the driver's 1/2/4/8-GPU runs give the north star's strong-scaling curve
@@ -33,7 +47,8 @@ event-timed duration against 8 TB/s; `roofline.cycle_frac` the compulsory bytes 
  over ms_per_step against 8 TB/s; `finest_smoother_GBps` BASELINE.md's definition
 3 sizeof(real) cells_per_rank sweeps / summed finest-level smoothing kernel time.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]  (N>1 under torch.distributed.run).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]  (N>1 under
+torch.distributed.run).
 """
 from __future__ import annotations
 
@@ -47,6 +62,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "lua-multigrid-poisson_amd"))
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: values of psi kept when the field holds more (16 MB fp32, 32 MB fp64)
+DUMP_SEED = 20240521  # seed of that sample's indices
 
 
 def parse(argv=None):
@@ -54,6 +71,11 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10, help="untimed cycles (graph capture, clocks)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: measured copy peak, event-timed roofline "
+                        "pass, relative residual, cpu_baseline, and (default workload) the fp64 and north-star lines")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the timed cycles returned (err.npy, psi.npy: see the module docstring) into DIR")
     p.add_argument("--n", type=int, default=512, help="cells per axis of each rank's cube slab (weak scaling)")
     p.add_argument("--box", default=None, help="NX,NY,NZ global box, strong scaling over the ranks (slab-z)")
     p.add_argument("--dim", type=int, default=3, choices=[2, 3])
@@ -67,18 +89,19 @@ def parse(argv=None):
     p.add_argument("--config0", action="store_true",
                    help="BASELINE configs[0]: 2D 256^2 fp64 Jacobi 7+7 V-cycle, injection, ghost 0 (cpu.lua path)")
     p.add_argument("--copy-probe-mb", type=int, default=2048,
-                   help="buffer size of the measured copy-bandwidth probe reported beside the roofline (0 = skip)")
-    p.add_argument("--no-timing", action="store_true", help="skip the per-launch smoother events")
+                   help="buffer size of the copy-bandwidth probe that ramps the clocks before the warmup and, with --full, "
+                        "is reported beside the roofline (0 = skip)")
+    p.add_argument("--no-timing", action="store_true", help="--full: skip the per-launch smoother events")
     p.add_argument("--plan-only", action="store_true",
                    help="no GPU: run the launch plumbing (process group, comm id broadcast, options) and print every "
                         "rank's level plan (mgp_plan, host logic) after checking that the ranks' slabs tile the box, "
                         "with each workload's per-cycle RCCL calls and bytes per rank (mgp_plan_comm)")
     p.add_argument("--no-north-star", action="store_true",
-                   help="with N >= 4: skip the configs[3] / configs[4] lines after the weak-scaling line")
+                   help="--full: skip the fp64 and configs[3] / configs[4] lines after the weak-scaling line")
     p.add_argument("--ns-steps", type=int, default=5, help="timed cycles of each north-star line")
     p.add_argument("--ns-warmup", type=int, default=2, help="untimed cycles of each north-star line")
     p.add_argument("--cpu-reps", type=int, default=3, help="cpu_baseline: best of this many timed samples")
-    p.add_argument("--cpu-cycles", type=int, default=4, help="oracle cycles timed for cpu_baseline (0 = skip)")
+    p.add_argument("--cpu-cycles", type=int, default=4, help="--full: oracle cycles timed for cpu_baseline (0 = skip)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="threads of the OpenMP cpu_baseline (0 = OMP_NUM_THREADS or all host cores)")
     p.add_argument("--traffic", default=",".join(os.path.join(ROOT, "profiles", f"pmc_traffic_{w}.json") for w in
@@ -153,7 +176,7 @@ def main():
 
 
 def want_north_star(a, world):
-    return not a.box and a.dim == 3 and not a.config0 and not a.no_north_star
+    return a.full and not a.box and a.dim == 3 and not a.config0 and not a.no_north_star
 
 
 def new_comm_id(dist, rank, world):
@@ -238,8 +261,8 @@ class env_override:
 
 
 def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, primary=False):
-    """One workload: K timed cycles (hipGraph replay on one GPU), then the same K again with event timing; returns
-    the bench line (meaningful on rank 0)."""
+    """One workload: K timed cycles (hipGraph replay on one GPU), then with --full the same K again with event
+    timing; returns the bench line (meaningful on rank 0)."""
     import torch
 
     import mgpoisson
@@ -262,7 +285,11 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
     # sustained GPU load, so the clocks have ramped when the warmup starts (MGP_BENCH_PROBE_LATE=1: after the timing)
     copy_peak = None
     probe_first = os.environ.get("MGP_BENCH_PROBE_LATE", "0") == "0"
-    if primary and a.copy_probe_mb > 0 and local == 0 and rank == 0 and probe_first:
+    # A plain run keeps the early probe for that ramp alone (a fraction of a second; its figure is reported with
+    # --full): without it the timed cycles of a short line still run on ramping clocks, measured at 512^3,
+    # --steps 20 --warmup 5: 1.030-1.038 ms per cycle without the probe, 1.013-1.017 ms with it (500 steps: equal)
+    probe = primary and a.copy_probe_mb > 0 and local == 0 and rank == 0
+    if probe and probe_first:
         copy_peak = mgpoisson.copy_bandwidth(local, a.copy_probe_mb << 20, 10)
     # warmup (untimed; also captures the hipGraphs of the cycle)
     if warmup:
@@ -272,12 +299,14 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
     errs = ctx.cycles(steps)
     barrier_sync()
     dt = time.perf_counter() - t0
+    if primary and a.dump_outputs:
+        dump_outputs(a.dump_outputs, ctx, errs, rank, world)  # (before anything else advances the solution)
 
     # roofline window: the same K cycles again, launched eagerly with a HIP event pair around
     # every timed level-0 launch and every exchange / collective on the stream it runs on (graph replay cannot
     # bracket single launches); the kernels are identical, only the host launch path differs
     timed, launched = {}, {}
-    if not a.no_timing:
+    if a.full and not a.no_timing:
         ctx.timing(True)
         ctx.cycles(steps)
         timed = ctx.timing_read()
@@ -285,7 +314,7 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
         ctx.timing(False)
         barrier_sync()
 
-    if primary and a.copy_probe_mb > 0 and local == 0 and rank == 0 and not probe_first:
+    if probe and a.full and not probe_first:
         copy_peak = mgpoisson.copy_bandwidth(local, a.copy_probe_mb << 20, 10)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64)
@@ -293,7 +322,7 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
         dt = float(t.item())
     comm = {k: timed.get(k, (0.0, 0, 0.0)) for k in ("exchange", "collective")}
     comm_all = [comm]
-    if world > 1:
+    if world > 1 and a.full:
         comm_all = [None] * world
         dist.all_gather_object(comm_all, comm)
 
@@ -325,7 +354,6 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
         tag = "BASELINE configs[2]: " if n == 512 else ""
         workload = f"{tag}3D Poisson {n}^3 per GPU, 7-point, {algo}"
         unit = f"{kind}-cycles/s ({n}^3-cell slabs, whole job)"
-    rnorm, fnorm = ctx.residual_norm()
     ms_step = 1e3 * dt / steps
     line = {
         "metric": "V-cycles/sec + finest-smoother achieved HBM GB/s, 3D Poisson",
@@ -348,10 +376,12 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
             "levels": len(ctx.levels),
         },
         "final_err": float(errs[-1]),
-        "relative_residual": rnorm / fnorm,
         "hbm_used_GB_rank0": (total_b - free_b) / 1e9,
     }
-    if world > 1:
+    if a.full:
+        rnorm, fnorm = ctx.residual_norm()
+        line["relative_residual"] = rnorm / fnorm
+    if world > 1 and a.full:
         # per rank and cycle: halo exchanges (grouped send/recv, either stream) and the all-gather / err all-reduce,
         # HIP-event time on the stream they run on (includes waiting for the neighbour), and what the rank sends
         line["comm_per_rank"] = [
@@ -450,7 +480,7 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
                           "time; the temporally blocked phases do nu sweeps per launch from one read of the level, so "
                           "this per-sweep figure is bounded by 8 TB/s x (sweeps per compulsory pass), not 8 TB/s"}
 
-    if primary and rank == 0 and world == 1 and a.cpu_cycles > 0:
+    if a.full and primary and rank == 0 and world == 1 and a.cpu_cycles > 0:
         thr = a.cpu_threads or int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or (os.cpu_count() or 1)
         # configs[0] is small: the CPU port runs the same cycles the GPU timed, in full
         c_omp, c_one = (steps, steps) if a.config0 else (a.cpu_cycles, max(1, a.cpu_cycles // 2))
@@ -458,6 +488,30 @@ def run_workload(a, cfg, box, strong, rank, world, local, dist, steps, warmup, p
         line["cpu_baseline_1thread"] = cpu_baseline(cfg, c_one, 1, gcells, a.cpu_reps)
     ctx.close()
     return line
+
+
+def dump_outputs(path, ctx, errs, rank, world):
+    """--dump-outputs: what the caller of the timed cycles received from them (module docstring): the per-cycle errs
+    (float64) and the finest-level solution after the last cycle, in the context's real type — the whole field up to
+    DUMP_SAMPLE values, else its values at DUMP_SAMPLE flat indices drawn once from DUMP_SEED and the field's
+    size (so the same in every run and build), in ascending order."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"err{sfx}.npy"), np.asarray(errs, dtype=np.float64))
+    psi = ctx.get_psi().reshape(-1)
+    if psi.size > DUMP_SAMPLE:
+        psi = psi[sample_indices(psi.size, DUMP_SAMPLE, DUMP_SEED)]
+    np.save(os.path.join(path, f"psi{sfx}.npy"), psi)
+
+
+def sample_indices(size, count, seed):
+    """`count` flat indices below `size`, ascending, the same for the same arguments (numpy's PCG64 stream is
+    stable across versions for integers())."""
+    import numpy as np
+
+    return np.sort(np.random.Generator(np.random.PCG64(seed)).integers(0, size, size=count, dtype=np.int64))
 
 
 def pick_traffic(paths, wkey, launched, src_hash=None):

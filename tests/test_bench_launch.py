@@ -44,6 +44,7 @@ def test_weak_scaling_launch_plan(n):
     assert d["rank_slabs_level0"] == [[512 * r, 512] for r in range(n)]
     assert d["engines"][0] == "zs" and d["distributed_levels"] >= 2
     assert d["comm_id_bytes"] == 128
+    assert "north_star_lines" not in d and "fp64_line" not in d  # a plain run: only with --full
 
 
 def test_strong_scaling_launch_plan_config3():
@@ -55,10 +56,10 @@ def test_strong_scaling_launch_plan_config3():
 
 
 def test_north_star_lines_planned_at_8_ranks():
-    """At 8 ranks the default run adds BASELINE configs[3] (2048^3 V) and configs[4] (4096^3 F) to the line;
+    """At 8 ranks the --full run adds BASELINE configs[3] (2048^3 V) and configs[4] (4096^3 F) to the line;
     --plan-only lists each workload's per-cycle RCCL calls and bytes per rank (mgp_plan_comm: the library's own
     cycle logic, run on the host with every device call skipped)."""
-    d = _launch(8)
+    d = _launch(8, "--full")
     assert set(d["north_star_lines"]) == {"configs[3]", "configs[4]"}
     weak = d["comm_per_cycle"]
     # weak scaling: level 0 (k_zs): u before PRE, u on the side stream after PRE; levels 1-4 (deep halos): f before
@@ -75,10 +76,11 @@ def test_north_star_lines_planned_at_8_ranks():
 
 @pytest.mark.parametrize("n", [1, 2])
 def test_north_star_lines_planned_at_1_and_2_ranks(n):
-    """the driver's 1- and 2-GPU runs carry the configs[3] whole-box line too (2048^3 fits one
+    """the 1- and 2-GPU --full runs carry the configs[3] whole-box line too (2048^3 fits one
     GPU: ~160 GB with u, f, t, psiOld and the hierarchy), so the 1/2/4/8 runs give the north star's strong-scaling
-    curve; configs[4] (4096^3) does not fit fewer than 4 GPUs and is listed as skipped.  N = 1 adds the fp64 line."""
-    d = _launch(n)
+    curve; configs[4] (4096^3) does not fit fewer than 4 GPUs and is listed as skipped.  N = 1 adds the fp64 line.
+    A plain run plans neither."""
+    d = _launch(n, "--full")
     ns = d["north_star_lines"]
     assert set(ns) == {"configs[3]", "configs[4]"}
     assert ns["configs[3]"]["fits"] and not ns["configs[4]"]["fits"]

@@ -8,7 +8,7 @@ for r in $(seq 1 ${REPS:-2}); do
   while IFS='|' read -r label envs args; do
     [ -z "$label" ] && continue
     out=gpurun_out/ab/${label}_$r.json
-    env $envs timeout -k 10 ${LIMIT:-300} python3 bench.py $args --cpu-cycles 0 --no-north-star --copy-probe-mb 0 > $out 2> gpurun_out/ab/${label}_$r.err
+    env $envs timeout -k 10 ${LIMIT:-300} python3 bench.py --full $args --cpu-cycles 0 --no-north-star --copy-probe-mb 0 > $out 2> ${out%.json}.err
     rc=$?
     python3 - "$out" "$label" <<'PY'
 import json, sys

@@ -2,7 +2,7 @@
 """One cycle of a rocprofv3 kernel trace, kernel by kernel (cycles delimited by the err sum k_sum_n).
 usage: cycle_breakdown.py run_kernel_trace.csv [cycle index from the end, default 3] [kernel=grid]
 With kernel=grid (e.g. "k_zs<float, true, 0=114688"), the index counts only the cycles holding a launch of that kernel
-with that grid size (a trace of bench.py's default run also holds its fp64 and north-star lines)."""
+with that grid size (a trace of bench.py's --full run also holds its fp64 and north-star lines)."""
 import csv
 import re
 import sys

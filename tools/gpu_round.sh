@@ -5,13 +5,14 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+O=$_  # the output folder just made (bash: the last argument of the previous command)
 PMC_GROUPS="FETCH_SIZE
 WRITE_SIZE" bash tools/pmc.sh || exit $?
 python3 tools/pmc_traffic.py gpurun_out/pmc gpurun_out/pmc_traffic.json "" > gpurun_out/pmc_traffic.txt || exit 1
 cat gpurun_out/pmc_traffic.txt
 echo "== bench"
-timeout -k 10 300 python bench.py --steps ${STEPS:-50} --warmup 3 --no-north-star --traffic gpurun_out/pmc_traffic.json > gpurun_out/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --steps ${STEPS:-50} --warmup 3 --no-north-star --traffic $O/pmc_traffic.json > $O/bench.log 2>&1
 rc=$?; tail -n 3 gpurun_out/bench.log; [ $rc -eq 0 ] || exit $rc
 echo "== prof"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --steps ${STEPS:-50} --warmup 3 --no-north-star --cpu-cycles 0 --traffic gpurun_out/pmc_traffic.json > gpurun_out/prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --steps ${STEPS:-50} --warmup 3 --no-north-star --cpu-cycles 0 --traffic $O/pmc_traffic.json > $O/prof.log 2>&1
 rc=$?; tail -n 2 gpurun_out/prof.log; exit $rc
