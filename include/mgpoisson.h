@@ -212,6 +212,49 @@ int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnor
 int         mgp_cg_solve(mgp_ctx* c, double epsilon, int32_t maxiter, void* x_out, int mem, int32_t* iters,
                          double* err, double* linf_hist);
 
+/* Mixed-precision defect correction (iterative refinement): the outer loop of cpu.lua:196-216 with real = 'double'
+ * — fp64 psi and f, err = sqrt(sum (psi - psiOld)^2 / N) in double — around the fp32 cycles of a real_bytes = 4,
+ * MGP_ARITH_REAL context.  One outer step: r = f - A psi in double (calcResidual, cpu.lua:108-123, on the fp64
+ * fields), narrowed to float into level 0's f; `inner` ordinary cycles of the context on A e = r from e = 0 in
+ * level 0's u; psi += (double)e.  The fp32 hierarchy, its engines and their bit-exactness are unchanged; no
+ * reference counterpart for the split itself (build-defined).  Limits: r is not rescaled before it is narrowed, so a
+ * right-hand side whose defect leaves float's normal range is out of scope; one GPU only.  Measured time to
+ * ||r|| / ||f|| <= 1e-12 against a real_bytes = 8 context (tools/refine_time.py, profiles/refine_time.json, one
+ * MI355X): 3D 512^3 0.75 / 0.79 / 0.81 of the double time with inner = 2 / 4 / 6; 2D 4096^2 0.89 / 1.27 / 1.77.
+ *
+ * mgp_refine_begin allocates the fp64 psi / f (level 0's shape) and fills them with the exact widening of level 0's
+ * current u / f.  MGP_ERR_ARG for real_bytes = 8 or MGP_ARITH_DOUBLE; MGP_ERR_STATE for world > 1, a loopback
+ * context, a group's rank context, MGP_TRANSPORT=rccl, or when already active; MGP_ERR_OOM leaves the context as it
+ * was.  While active, level 0's fp32 f / u are the scratch of the inner solve (mgp_get_field returns the last
+ * narrowed defect / the last correction e); mgp_cycle, mgp_cycles, mgp_two_grid, mgp_metrics, mgp_cg_solve and
+ * level-0 mgp_set_field / mgp_set_planes return MGP_ERR_STATE; mgp_init_point_charge also sets the fp64 fields.
+ * mgp_refine_end stores the round-to-nearest narrowing of psi / f into level 0's u / f and frees the fp64 fields
+ * (mgp_destroy frees them as well): an ordinary fp32 context again.  Every mgp_refine_* call but begin returns
+ * MGP_ERR_STATE while refinement is not active. */
+enum { MGP_REFINE_PSI = 0, MGP_REFINE_F = 1 };
+int         mgp_refine_begin(mgp_ctx* c);
+int         mgp_refine_end(mgp_ctx* c);
+/* mg.psi / mg.f of the double solver (cpu.lua:179-193): the whole fp64 field, x fastest; count = level 0's cells;
+ * host or device memory, through the bounded staging buffer. */
+int         mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int mem);
+int         mgp_refine_get(const mgp_ctx* c, int which, double* dst, int64_t count, int mem);
+/* *rnorm = ||f - A psi||_2, *fnorm = ||f||_2 of the fp64 fields (fp64 sums: per wave, per workgroup, fixed order);
+ * psi is not changed (level 0's fp32 f receives the narrowed defect). */
+int         mgp_refine_residual(mgp_ctx* c, double* rnorm, double* fnorm);
+/* One outer step = MultigridCPU:step() (cpu.lua:196-206) of the double solver with `inner` >= 1 fp32 cycles in place
+ * of its one twoGrid: the defect from a zero guess, the cycles (the path mgp_cycles takes: graph replay, or eager
+ * under mgp_timing / mgp_set_debug / a hand-off; their own errs are discarded), the add; one host synchronisation.
+ * *rnorm / *fnorm: of the defect, i.e. before this step's correction; *err = sqrt(sum e^2 / N) (cpu.lua:203: psi -
+ * psiOld is e).  With mgp_set_debug(1) the narrowed defect and every phase of the cycles are scanned: a NaN or inf
+ * in the fp64 fields fails the step with "found a nan" (MGP_ERR_STATE). */
+int         mgp_refine_step(mgp_ctx* c, int32_t inner, double* rnorm, double* fnorm, double* err);
+/* MultigridCPU:solve() (cpu.lua:208-216) over that step: computes the defect and stops when rnorm <= rtol * fnorm
+ * (checked before any cycle is spent), when a step's err < epsilon, when a norm or err is not finite, or after
+ * maxouter steps.  rel_hist (maxouter + 1 doubles, may be NULL): rnorm / fnorm of every defect computed; err_hist
+ * (maxouter doubles, may be NULL): each step's err; *steps: steps done. */
+int         mgp_refine_solve(mgp_ctx* c, int32_t inner, double rtol, double epsilon, int32_t maxouter,
+                             int32_t* steps, double* rel_hist, double* err_hist);
+
 /* Loopback transport (tests only): the `world` ranks of a slab decomposition as contexts of ONE
  * process on one GPU, each driven by its own host thread.  Halo exchanges, the all-gather and the
  * err all-reduce become device copies ordered by events and a host barrier instead of RCCL calls;
@@ -263,10 +306,12 @@ int         mgp_set_debug(mgp_ctx* c, int mode);
  *   MGP_TIMING_EXCHANGE    every halo exchange of any level (grouped send/recv with the z-neighbours, on the
  *                          compute or the side stream); bytes = what this rank sends
  *   MGP_TIMING_COLLECTIVE  the agglomeration all-gather and the err all-reduce; bytes = what this rank sends
+ *   MGP_TIMING_REFINE_DEFECT / _ADD  the two fp64 passes of mgp_refine_residual / _step / _solve (with their
+ *                          final sums): 24 (20 without the zero guess) and 20 bytes per cell
  * mgp_timing_read returns, for one kind, the summed milliseconds, the number of timed launches / calls and
  * their bytes (algorithmic for the kernels: SURVEY.md §8d, not measured traffic). */
 enum { MGP_TIMING_HALF_SWEEP = 0, MGP_TIMING_FUSED_PRE = 1, MGP_TIMING_FUSED_POST = 2, MGP_TIMING_EXCHANGE = 3,
-       MGP_TIMING_COLLECTIVE = 4, MGP_TIMING_KINDS = 5 };
+       MGP_TIMING_COLLECTIVE = 4, MGP_TIMING_REFINE_DEFECT = 5, MGP_TIMING_REFINE_ADD = 6, MGP_TIMING_KINDS = 7 };
 int         mgp_timing(mgp_ctx* c, int enable);
 int         mgp_timing_read(mgp_ctx* c, int kind, double* ms_total, int64_t* launches, double* bytes);
 /* The kernel the last timed launch of a kind ran (MGP_TIMING_FUSED_PRE / _POST; level 0): its symbol with the

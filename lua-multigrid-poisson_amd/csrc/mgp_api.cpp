@@ -276,6 +276,13 @@ struct mgp_ctx {
     size_t stage_bytes = 0;
     uint64_t* d_stats_h = nullptr;  // mgp_field_stats scratch: kSumBlocks + 1 hashes, then 3 kSumBlocks + 3 doubles
     double* d_part = nullptr;
+    // Mixed-precision defect correction (mgp_refine_begin .. mgp_refine_end): the fp64 psi and f of level 0, in
+    // its packed layout with its ghost planes, and the reduction scratch of the two fp64 passes
+    // (refine_partials() partials, then {sum r^2, sum f^2, sum e^2})
+    char* psi64 = nullptr;
+    char* f64 = nullptr;
+    double* d_ref = nullptr;
+    bool refining() const { return psi64 != nullptr; }
     std::map<char*, char*> pad_base;  // (MGP_PAD_BYTES) offset pointer -> its allocation
     size_t pad = 0;                   // MGP_PAD_BYTES at creation
     int64_t part_cap = 0;
@@ -2110,6 +2117,9 @@ static void destroy_impl(mgp_ctx* c)
     if (c->psi_old) (void)hipFree(c->psi_old);
     if (c->rscratch) (void)hipFree(c->rscratch);
     if (c->xbuf) dev_free(c, c->xbuf);
+    if (c->psi64) dev_free(c, c->psi64);
+    if (c->f64) dev_free(c, c->f64);
+    if (c->d_ref) (void)hipFree(c->d_ref);
     if (c->stage) (void)hipFree(c->stage);
     if (c->d_stats_h) (void)hipFree(c->d_stats_h);
     if (c->d_part) (void)hipFree(c->d_part);
@@ -2464,6 +2474,16 @@ int mgp_level_info(const mgp_ctx* c, int level, int64_t info[8])
     return MGP_OK;
 }
 
+// While mixed-precision refinement is active, level 0's u and f belong to its inner solve
+static int refine_refuses(mgp_ctx* c, const char* what)
+{
+    return c->fail(MGP_ERR_STATE, "%s: mixed-precision refinement is active (mgp_refine_begin): level 0's u and f are "
+                                  "the scratch of its inner solve; use mgp_refine_* or call mgp_refine_end first", what);
+}
+
+// interior plane 0 of a level-0-shaped fp64 field
+static double* ui64(const mgp_ctx* c, char* base) { return (double*)(base + (size_t)(c->G * c->lev[0].g.P) * 8); }
+
 int mgp_init_point_charge(mgp_ctx* c)
 {
     if (!c) return MGP_ERR_ARG;
@@ -2471,6 +2491,9 @@ int mgp_init_point_charge(mgp_ctx* c)
     const int64_t cz = c->o.dim == 3 ? L.p.gnz / 2 : 0;
     HIP_TRY(c, mgp::launch_init_point_charge(c->rb, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), L.g, L.p.nx / 2,
                                              L.p.ny / 2, cz, c->s));
+    if (c->refining())  // (+-1e6 is exact in both types)
+        HIP_TRY(c, mgp::launch_init_point_charge(8, c->o.dim, ui64(c, c->psi64), ui64(c, c->f64), L.g, L.p.nx / 2,
+                                                 L.p.ny / 2, cz, c->s));
     fields_written(c);
     return sync_and_check(c);
 }
@@ -2604,6 +2627,7 @@ int mgp_set_field(mgp_ctx* c, int level, int which, const void* src, int64_t cou
 {
     if (!c) return MGP_ERR_ARG;
     if (check_level(c, level) != MGP_OK) return c->fail(MGP_ERR_ARG, "mgp_set_field: bad level %d", level);
+    if (level == 0 && c->refining()) return refine_refuses(c, "mgp_set_field(level 0)");
     Level& L = c->lev[level];
     if (count != level_count(L))
         return c->fail(MGP_ERR_ARG, "mgp_set_field: count %lld != %lld", (long long)count, (long long)level_count(L));
@@ -2624,6 +2648,7 @@ int mgp_get_field(const mgp_ctx* cc, int level, int which, void* dst, int64_t co
 int mgp_set_planes(mgp_ctx* c, int level, int which, int64_t z_begin, int64_t nz, const void* src, int mem)
 {
     if (!c) return MGP_ERR_ARG;
+    if (level == 0 && c->refining()) return refine_refuses(c, "mgp_set_planes(level 0)");
     return planes_io(c, level, which, z_begin, nz, const_cast<void*>(src), mem, true);
 }
 
@@ -2656,9 +2681,33 @@ int mgp_field_stats(const mgp_ctx* cc, int level, int which, uint64_t* hash, dou
     return MGP_OK;
 }
 
-int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
+// mgp_set_debug: a fresh record of checks before a call's first phase
+static int debug_reset(mgp_ctx* c)
 {
-    if (!c || k < 0) return MGP_ERR_ARG;
+    if (!c->debug) return MGP_OK;
+    c->dbg_names.clear();
+    HIP_TRY(c, hipMemsetAsync(c->d_dbg, 0x7f, sizeof(int), c->s));
+    return MGP_OK;
+}
+
+// ... and its verdict after the call's synchronisation
+static int debug_verdict(mgp_ctx* c)
+{
+    if (!c->debug) return MGP_OK;
+    int first = 0;
+    HIP_TRY(c, hipMemcpy(&first, c->d_dbg, sizeof(int), hipMemcpyDeviceToHost));
+    if (first >= 0 && first < (int)c->dbg_names.size()) {
+        c->fail_after_sync = true;
+        return c->fail(MGP_ERR_STATE, "found a nan (cpu-raw.lua:135-139, gpu.lua:279-283): %s",
+                       c->dbg_names[(size_t)first].c_str());
+    }
+    return MGP_OK;
+}
+
+// k outer iterations enqueued on the stream (graph replay where it is on), their errs in d_errs[0 .. k); no
+// synchronisation.  mgp_cycles, and the inner cycles of mgp_refine_step.
+static int enqueue_cycles(mgp_ctx* c, int32_t k)
+{
     TRY(ensure_errs(c, k));
     const bool graph = c->use_graph && !c->timing && !c->handoff_fn && !c->debug;
     // one GPU: every cycle's err goes to d_errs[*d_slot] and advances the device counter (graph replays
@@ -2666,27 +2715,23 @@ int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
     const bool ctr = !c->multi() && c->o.err_mode && k > 0;
     if (ctr) HIP_TRY(c, hipMemsetAsync(c->d_slot, 0, sizeof(int), c->s));
     c->err_ctr = ctr ? c->d_slot : nullptr;
-    if (c->debug) {
-        c->dbg_names.clear();
-        HIP_TRY(c, hipMemsetAsync(c->d_dbg, 0x7f, sizeof(int), c->s));
-    }
     int rc = MGP_OK;
     for (int i = 0; i < k && rc == MGP_OK; ++i) {
         c->dbg_cycle = i + 1;
         rc = graph ? graph_cycle(c, i) : one_cycle(c, ctr ? c->d_errs : c->d_errs + i);
     }
     c->err_ctr = nullptr;
-    TRY(rc);
+    return rc;
+}
+
+int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
+{
+    if (!c || k < 0) return MGP_ERR_ARG;
+    if (c->refining()) return refine_refuses(c, "mgp_cycles");
+    TRY(debug_reset(c));
+    TRY(enqueue_cycles(c, k));
     TRY(sync_and_check(c));
-    if (c->debug) {
-        int first = 0;
-        HIP_TRY(c, hipMemcpy(&first, c->d_dbg, sizeof(int), hipMemcpyDeviceToHost));
-        if (first >= 0 && first < (int)c->dbg_names.size()) {
-            c->fail_after_sync = true;
-            return c->fail(MGP_ERR_STATE, "found a nan (cpu-raw.lua:135-139, gpu.lua:279-283): %s",
-                           c->dbg_names[(size_t)first].c_str());
-        }
-    }
+    TRY(debug_verdict(c));
     if (errs) {
         if (!c->o.err_mode) {
             for (int i = 0; i < k; ++i) errs[i] = NAN;
@@ -2714,6 +2759,7 @@ int mgp_cycle(mgp_ctx* c, double* err_out)
 int mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int mem)
 {
     if (!c || !u || !f) return MGP_ERR_ARG;
+    if (c->refining()) return refine_refuses(c, "mgp_two_grid");
     if (c->o.world > 1) return c->fail(MGP_ERR_STATE, "mgp_two_grid: single-GPU contexts only");
     for (int l = 0; l < (int)c->lev.size(); ++l) {
         Level& Lv = c->lev[l];
@@ -2850,6 +2896,7 @@ int mgp_set_coarse_handoff(mgp_ctx* c, int64_t size, mgp_coarse_fn fn, void* use
 int mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* frob)
 {
     if (!c) return MGP_ERR_ARG;
+    if (c->refining()) return refine_refuses(c, "mgp_metrics");
     if (!c->metrics_old)
         return c->fail(MGP_ERR_STATE, "mgp_metrics: no psiOld of a last outer iteration (run mgp_cycle with err_mode 1; "
                                       "not kept with MGP_KEEP_PSI_OLD=0 on the temporally blocked finest level)");
@@ -2908,10 +2955,246 @@ int mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm)
     return MGP_OK;
 }
 
+// ---- mixed-precision defect correction (cpu.lua:196-216 with real = 'double', around the fp32 cycles) ----
+
+static int refine_active(mgp_ctx* c, const char* what)
+{
+    if (c->refining()) return MGP_OK;
+    return c->fail(MGP_ERR_STATE, "%s: mixed-precision refinement is not active (call mgp_refine_begin first)", what);
+}
+
+static void refine_release(mgp_ctx* c)
+{
+    for (char** p : {&c->psi64, &c->f64}) {
+        if (!*p) continue;
+        dev_free(c, *p);
+        c->pad_base.erase(*p);
+        *p = nullptr;
+    }
+    if (c->d_ref) (void)hipFree(c->d_ref);
+    c->d_ref = nullptr;
+}
+
+int mgp_refine_begin(mgp_ctx* c)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (c->o.real_bytes != 4 || c->o.arith != MGP_ARITH_REAL)
+        return c->fail(MGP_ERR_ARG, "mgp_refine_begin: the inner cycles are those of a real_bytes = 4, MGP_ARITH_REAL "
+                                    "context (a double context needs no refinement)");
+    if (c->multi() || c->lb || c->group_stop || c->nb_comm)
+        return c->fail(MGP_ERR_STATE, "mgp_refine_begin: one GPU only (not world > 1, a loopback or group rank "
+                                      "context, or MGP_TRANSPORT=rccl)");
+    if (c->refining()) return c->fail(MGP_ERR_STATE, "mgp_refine_begin: refinement is already active");
+    Level& L = c->lev[0];
+    TRY(materialize_zero(c, L));
+    TRY(sync_and_check(c));  // (nothing is in flight through the staging buffer, which may be replaced)
+    const size_t bytes = (size_t)L.alloc * 8;
+    // the staging buffer of field I/O holds whole lexicographic planes: at least one fp64 plane from here on
+    const size_t plane64 = (size_t)(L.p.nx * L.p.ny) * 8;
+    char* stage = nullptr;
+    if (c->stage_bytes < plane64 && hipMalloc(&stage, plane64) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(MGP_ERR_OOM, "mgp_refine_begin: no room for the fp64 staging plane");
+    }
+    if (dev_alloc(c, &c->psi64, bytes, 5) != hipSuccess || dev_alloc(c, &c->f64, bytes, 6) != hipSuccess ||
+        hipMalloc(&c->d_ref, sizeof(double) * ((size_t)mgp::refine_partials() + 4)) != hipSuccess) {
+        (void)hipGetLastError();
+        refine_release(c);
+        if (stage) (void)hipFree(stage);
+        return c->fail(MGP_ERR_OOM, "mgp_refine_begin: hipMalloc failed for the fp64 psi and f (2 x %zu bytes)", bytes);
+    }
+    if (stage) {
+        (void)hipFree(c->stage);
+        c->stage = stage;
+        c->stage_bytes = plane64;
+    }
+    // zero ghost planes for the context's lifetime, the interior = the exact widening of the current u / f
+    const int64_t n = L.g.P * L.g.nz;
+    HIP_TRY(c, hipMemsetAsync(c->psi64, 0, bytes, c->s));
+    HIP_TRY(c, hipMemsetAsync(c->f64, 0, bytes, c->s));
+    HIP_TRY(c, mgp::launch_refine_widen((const float*)c->ui(L, L.u), ui64(c, c->psi64), n, c->s));
+    HIP_TRY(c, mgp::launch_refine_widen((const float*)c->ui(L, L.f), ui64(c, c->f64), n, c->s));
+    c->metrics_old = nullptr;  // psiOld of an fp32 outer iteration means nothing to the refinement
+    return sync_and_check(c);
+}
+
+int mgp_refine_end(mgp_ctx* c)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(refine_active(c, "mgp_refine_end"));
+    Level& L = c->lev[0];
+    const int64_t n = L.g.P * L.g.nz;
+    HIP_TRY(c, mgp::launch_refine_narrow(ui64(c, c->psi64), (float*)c->ui(L, L.u), n, c->s));
+    HIP_TRY(c, mgp::launch_refine_narrow(ui64(c, c->f64), (float*)c->ui(L, L.f), n, c->s));
+    fields_written(c);
+    c->metrics_old = nullptr;
+    const int rc = sync_and_check(c);
+    refine_release(c);
+    return rc;
+}
+
+// mgp_refine_set / _get: the whole fp64 field <-> the caller's lexicographic buffer, in plane chunks through the
+// bounded staging buffer (planes_io at rb = 8)
+static int refine_io(mgp_ctx* c, int which, void* buf, int64_t count, int mem, bool to_device, const char* what)
+{
+    TRY(refine_active(c, what));
+    Level& L = c->lev[0];
+    if ((which != MGP_REFINE_PSI && which != MGP_REFINE_F) || !buf)
+        return c->fail(MGP_ERR_ARG, "%s: which must be MGP_REFINE_PSI or MGP_REFINE_F, and the buffer not NULL", what);
+    if (count != level_count(L))
+        return c->fail(MGP_ERR_ARG, "%s: count %lld != %lld", what, (long long)count, (long long)level_count(L));
+    double* base = ui64(c, which == MGP_REFINE_PSI ? c->psi64 : c->f64);
+    const int64_t lex_plane = L.p.nx * L.p.ny;
+    const int64_t nz = L.g.nz;
+    const int64_t per_chunk =
+        mem == MGP_MEM_DEVICE ? nz : std::max<int64_t>(1, (int64_t)(c->stage_bytes / ((size_t)lex_plane * 8)));
+    for (int64_t z = 0; z < nz; z += per_chunk) {
+        const int64_t cn = std::min(per_chunk, nz - z);
+        Geo gs = L.g;
+        gs.nz = cn;
+        gs.z0 = L.g.z0 + z;
+        double* packed = base + z * L.g.P;
+        double* hb = (double*)buf + z * lex_plane;
+        const size_t bytes = (size_t)(cn * lex_plane) * 8;
+        if (to_device) {
+            const void* lex = hb;
+            if (mem != MGP_MEM_DEVICE) {
+                HIP_TRY(c, hipMemcpyAsync(c->stage, hb, bytes, hipMemcpyHostToDevice, c->s));
+                lex = c->stage;
+            }
+            HIP_TRY(c, mgp::launch_pack(8, lex, packed, gs, c->s));
+        } else {
+            void* lex = mem == MGP_MEM_DEVICE ? (void*)hb : (void*)c->stage;
+            HIP_TRY(c, mgp::launch_unpack(8, packed, lex, gs, c->s));
+            if (mem != MGP_MEM_DEVICE) {
+                HIP_TRY(c, hipMemcpyAsync(hb, c->stage, bytes, hipMemcpyDeviceToHost, c->s));
+                TRY(stream_wait(c, c->s));  // the next chunk reuses the staging buffer
+            }
+        }
+    }
+    return sync_and_check(c);
+}
+
+int mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int mem)
+{
+    if (!c) return MGP_ERR_ARG;
+    return refine_io(c, which, const_cast<double*>(src), count, mem, true, "mgp_refine_set");
+}
+
+int mgp_refine_get(const mgp_ctx* cc, int which, double* dst, int64_t count, int mem)
+{
+    mgp_ctx* c = const_cast<mgp_ctx*>(cc);
+    if (!c) return MGP_ERR_ARG;
+    return refine_io(c, which, dst, count, mem, false, "mgp_refine_get");
+}
+
+// The defect pass enqueued: level 0's f = (float)(f64 - A psi64), with `zero` its u = +0 (the inner cycles' guess);
+// sums to d_ref's results [0], [1]
+static int refine_defect(mgp_ctx* c, bool zero)
+{
+    Level& L = c->lev[0];
+    double* out = c->d_ref + mgp::refine_partials();
+    const double cells = (double)level_count(L);
+    hipEvent_t e;
+    TRY(timed_begin_on(c, c->s, &e));
+    HIP_TRY(c, mgp::launch_defect(c->o.dim, ui64(c, c->psi64), ui64(c, c->f64), (float*)c->ui(L, L.f),
+                                  zero ? (float*)c->ui(L, L.u) : nullptr, L.g, level_h(c, 0), c->d_ref, out, c->s));
+    TRY(timed_end_on(c, c->s, e, MGP_TIMING_REFINE_DEFECT, (zero ? 24.0 : 20.0) * cells));
+    fields_written(c);
+    c->metrics_old = nullptr;
+    c->dbg_cycle = 0;
+    return debug_check(c, 0, "the defect f - A psi of the fp64 fields, narrowed (f of level 0)", true);
+}
+
+// ... and the add: psi64 += (double)u of level 0, sum e^2 to d_ref's result [2]
+static int refine_add(mgp_ctx* c)
+{
+    Level& L = c->lev[0];
+    double* out = c->d_ref + mgp::refine_partials();
+    hipEvent_t e;
+    TRY(timed_begin_on(c, c->s, &e));
+    HIP_TRY(c, mgp::launch_refine_add(ui64(c, c->psi64), (const float*)c->ui(L, L.u), L.g, c->d_ref, out + 2, c->s));
+    return timed_end_on(c, c->s, e, MGP_TIMING_REFINE_ADD, 20.0 * (double)level_count(L));
+}
+
+// results [first, first + n) of the fp64 passes, after a synchronisation
+static int refine_read(mgp_ctx* c, int first, int n, double* h)
+{
+    HIP_TRY(c, hipMemcpyAsync(h, c->d_ref + mgp::refine_partials() + first, sizeof(double) * (size_t)n,
+                              hipMemcpyDeviceToHost, c->s));
+    return sync_and_check(c);
+}
+
+int mgp_refine_residual(mgp_ctx* c, double* rnorm, double* fnorm)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(refine_active(c, "mgp_refine_residual"));
+    TRY(debug_reset(c));
+    TRY(refine_defect(c, false));
+    double h[2];
+    TRY(refine_read(c, 0, 2, h));
+    if (rnorm) *rnorm = std::sqrt(h[0]);
+    if (fnorm) *fnorm = std::sqrt(h[1]);
+    return MGP_OK;
+}
+
+int mgp_refine_step(mgp_ctx* c, int32_t inner, double* rnorm, double* fnorm, double* err)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(refine_active(c, "mgp_refine_step"));
+    if (inner < 1) return c->fail(MGP_ERR_ARG, "mgp_refine_step: inner must be >= 1 (got %d)", (int)inner);
+    TRY(debug_reset(c));
+    TRY(refine_defect(c, true));
+    TRY(enqueue_cycles(c, inner));
+    TRY(refine_add(c));
+    double h[3];
+    TRY(refine_read(c, 0, 3, h));
+    TRY(debug_verdict(c));
+    if (rnorm) *rnorm = std::sqrt(h[0]);
+    if (fnorm) *fnorm = std::sqrt(h[1]);
+    if (err) *err = std::sqrt(h[2] / (double)c->ncells_global());  // cpu.lua:203
+    return MGP_OK;
+}
+
+int mgp_refine_solve(mgp_ctx* c, int32_t inner, double rtol, double epsilon, int32_t maxouter, int32_t* steps,
+                     double* rel_hist, double* err_hist)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(refine_active(c, "mgp_refine_solve"));
+    if (inner < 1 || maxouter < 0)
+        return c->fail(MGP_ERR_ARG, "mgp_refine_solve: inner >= 1 and maxouter >= 0 required (got %d, %d)", (int)inner,
+                       (int)maxouter);
+    if (steps) *steps = 0;
+    const double n = (double)c->ncells_global();
+    for (int32_t k = 0;; ++k) {
+        // the defect of the current psi; its zero guess only when a step may follow
+        TRY(debug_reset(c));
+        TRY(refine_defect(c, k < maxouter));
+        double h[2];
+        TRY(refine_read(c, 0, 2, h));
+        TRY(debug_verdict(c));
+        const double rn = std::sqrt(h[0]), fn = std::sqrt(h[1]);
+        if (rel_hist) rel_hist[k] = rn / fn;
+        if (!std::isfinite(rn) || !std::isfinite(fn) || rn <= rtol * fn || k >= maxouter) break;
+        TRY(debug_reset(c));
+        TRY(enqueue_cycles(c, inner));
+        TRY(refine_add(c));
+        double e2;
+        TRY(refine_read(c, 2, 1, &e2));
+        TRY(debug_verdict(c));
+        const double e = std::sqrt(e2 / n);
+        if (err_hist) err_hist[k] = e;
+        if (steps) *steps = k + 1;
+        if (e < epsilon || !std::isfinite(e)) break;  // cpu.lua:214
+    }
+    return MGP_OK;
+}
+
 int mgp_cg_solve(mgp_ctx* c, double epsilon, int32_t maxiter, void* x_out, int mem, int32_t* iters, double* err,
                  double* linf_hist)
 {
     if (!c || maxiter < 0) return MGP_ERR_ARG;
+    if (c->refining()) return refine_refuses(c, "mgp_cg_solve");
     if (c->o.world > 1) return c->fail(MGP_ERR_STATE, "mgp_cg_solve: single-GPU contexts only");
     Level& L = c->lev[0];
     const size_t bytes = (size_t)L.alloc * c->rb;

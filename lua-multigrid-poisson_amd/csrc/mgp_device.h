@@ -250,6 +250,36 @@ __device__ __forceinline__ int64_t pidx(const Geo& g, int i, int j, int64_t k)
     return k * g.P + c * g.H + (int64_t)j * g.hw + (i >> 1);
 }
 
+// thread per packed slot: slot -> (k, c, j, m) -> i = 2m + (c ^ parity); i >= nx only when nx = 1.  A plane stride
+// beyond 2 H (MGP_PLANE_PAD) leaves pad slots after each plane's two halves: no cell (they stay 0)
+__device__ __forceinline__ bool slot_cell(int64_t s, const Geo& g, int& i, int& j, int64_t& k)
+{
+    int64_t r = s;
+    bool pad = false;
+    if (g.P == 2 * g.H) {
+        k = s >> (g.lhw + g.ly + 1);
+    } else {
+        k = s / g.P;
+        r = s - k * g.P;
+        pad = r >= 2 * g.H;
+    }
+    const int m = (int)(r & (g.hw - 1));
+    j = (int)((r >> g.lhw) & (g.ny - 1));
+    const int c = (int)((r >> (g.lhw + g.ly)) & 1);
+    const int p = (int)((j + g.z0 + k) & 1);
+    i = 2 * m + (c ^ p);
+    return i < g.nx && !pad;
+}
+
+// Fixed-order fp64 sum across the 64 lanes of a wave (butterfly over lane distances 32 .. 1; every
+// lane ends with the same value, the same on every run).
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 __device__ __forceinline__ int xcd_remap(int b, int nblocks)
 {
     // blocks b and b + 8 share an XCD: hand each XCD a contiguous band of the grid (z-neighbour

@@ -135,6 +135,24 @@ hipError_t launch_residual_norm(int rb, int dim, const void* u, const void* f, G
 int sum_scratch(int n);
 hipError_t launch_sum_partials(const double* partials, int n, double* out, hipStream_t s, int* ctr = nullptr);
 
+// Mixed-precision defect correction on level 0 (mgp_refine.hip, mgp_refine_*): fp64 psi64 / f64 in level 0's packed
+// layout (same element offsets and ghost planes as the fp32 fields; pointers to interior plane 0).
+// launch_defect: r = f64 - A psi64 in double (Op<double, DIM>::residual, cl = 0, ghost 0: bit for bit
+// launch_residual_field(rb = 8)), (float)r to r32, +0.0f to u32_or_null when set (every packed slot, as a memset
+// would leave it); out[0] = sum r^2 (before narrowing), out[1] = sum f64^2, fp64 in fixed order.
+// launch_refine_add: psi64 += (double)e32 over the interior planes; out[0] = sum e32^2.
+// partials: refine_partials() doubles.  Rows of >= 4 cells take the 16-byte form (grid-stride and XCD-banded from
+// 2^20 two-cell items: defect_blocks() == 2048), shorter rows a thread per slot.
+int defect_blocks(Geo g);
+int refine_add_blocks(Geo g);
+int refine_partials();
+hipError_t launch_defect(int dim, const double* psi64, const double* f64, float* r32, float* u32_or_null, Geo g,
+                         double h, double* partials, double* out, hipStream_t s);
+hipError_t launch_refine_add(double* psi64, const float* e32, Geo g, double* partials, double* out, hipStream_t s);
+// exact widening / round-to-nearest narrowing of n packed reals
+hipError_t launch_refine_widen(const float* src, double* dst, int64_t n, hipStream_t s);
+hipError_t launch_refine_narrow(const double* src, float* dst, int64_t n, hipStream_t s);
+
 // Temporally blocked smoothing phases of a replicated 3D red/black level (ns = 2 sweeps):
 //   pre : dst = nu1 sweeps of src; R (coarse packed, Geo gc) = restrict(residual(dst))
 //   post: dst = nu2 sweeps of (src + P V); with partials, sum (dst - dst_before)^2 per workgroup

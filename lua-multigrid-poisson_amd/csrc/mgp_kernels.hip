@@ -36,26 +36,7 @@ namespace {
 
 // ---- init / pack / unpack -------------------------------------------------------------------
 
-// thread per packed slot: slot -> (k, c, j, m) -> i = 2m + (c ^ parity); i >= nx only when nx = 1.  A plane stride
-// beyond 2 H (MGP_PLANE_PAD) leaves pad slots after each plane's two halves: no cell (they stay 0)
-__device__ __forceinline__ bool slot_cell(int64_t s, const Geo& g, int& i, int& j, int64_t& k)
-{
-    int64_t r = s;
-    bool pad = false;
-    if (g.P == 2 * g.H) {
-        k = s >> (g.lhw + g.ly + 1);
-    } else {
-        k = s / g.P;
-        r = s - k * g.P;
-        pad = r >= 2 * g.H;
-    }
-    const int m = (int)(r & (g.hw - 1));
-    j = (int)((r >> g.lhw) & (g.ny - 1));
-    const int c = (int)((r >> (g.lhw + g.ly)) & 1);
-    const int p = (int)((j + g.z0 + k) & 1);
-    i = 2 * m + (c ^ p);
-    return i < g.nx && !pad;
-}
+// (slot_cell: mgp_device.h)
 
 // Element-wise kernels over every packed slot of a level run grid-stride over at most kMaxBlocks
 // workgroups: a 4096 x 4096 x 512 slab has 8.6e9 slots, past the 2^32 work-items one launch allows.
@@ -526,14 +507,7 @@ __device__ __forceinline__ C residual_at(const T* __restrict__ u, const T* __res
 
 // ---- residual norm (north star: wavefront-level reductions for the residual norm) -------------
 
-// Fixed-order fp64 sum across the 64 lanes of a wave (butterfly over lane distances 32 .. 1; every
-// lane ends with the same value, the same on every run).
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
+// (wave_sum: mgp_device.h)
 
 // sum (f - A u)^2 and sum f^2 over both colours of a level (calcResidual, cpu.lua:108-123, squared
 // and reduced on the device instead of materialising r).  Vector form: a thread owns N cells of one

@@ -31,6 +31,12 @@ It accepts the constructor protocols of the reference:
     (mgp_group_*); fields are the global box.
 mg:metrics() returns relErr, count, frobErr of the last outer iteration (gpu.lua:173-200);
 mg:residualNorm() returns ||f - A psi||, ||f|| (device reduction).
+real = 'mixed' (this build's addition; MG{size=n, real='mixed', ...} or MG(size, 'mixed')): mg.psi / mg.f are
+double, and mg:step() is one step of mixed-precision defect correction (mgp_refine_step): the defect
+f - A psi in double, mg.innerCycles (default 4) float cycles on it from a zero guess, psi = psi + e in
+double; the err it returns is the double solver's (cpu.lua:203).  mg:solve() keeps cpu.lua:208-216's
+loop over that step; mg:twoGrid raises; mg:refineResidual() returns ||f - A psi||, ||f|| of the double
+fields.  One GPU only (ngpu > 1 raises).
 Extra table fields select the build's configurations: dim (2|3), real, smoother ('jacobi'|'rbgs'|'gs_lex'),
 cycle ('V'|'F'), prolong ('pc'|'linear'), coarse_init ('fresh'|'warm'), coarse_bc
 ('zero'|'consistent'), restriction ('average'|'full_weighting'), arith ('real'|'double'), device.
@@ -89,6 +95,14 @@ int         mgp_set_coarse_handoff(mgp_ctx* c, int64_t size, mgp_coarse_fn fn, v
 int         mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* frob);
 int         mgp_set_debug(mgp_ctx* c, int mode);
 int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm);
+int         mgp_refine_begin(mgp_ctx* c);
+int         mgp_refine_end(mgp_ctx* c);
+int         mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int mem);
+int         mgp_refine_get(const mgp_ctx* c, int which, double* dst, int64_t count, int mem);
+int         mgp_refine_residual(mgp_ctx* c, double* rnorm, double* fnorm);
+int         mgp_refine_step(mgp_ctx* c, int32_t inner, double* rnorm, double* fnorm, double* err);
+int         mgp_refine_solve(mgp_ctx* c, int32_t inner, double rtol, double epsilon, int32_t maxouter,
+                             int32_t* steps, double* rel_hist, double* err_hist);
 int         mgp_group_create(mgp_group** out, const mgp_opts* o, int ngpu, const int* devices);
 mgp_ctx*    mgp_group_rank(mgp_group* g, int rank);
 void        mgp_group_destroy(mgp_group* g);
@@ -176,6 +190,7 @@ MultigridHIP.smooth = 7
 MultigridHIP.epsilon = 1e-10
 MultigridHIP.accuracy = 1e-10
 MultigridHIP.maxiter = 1000
+MultigridHIP.innerCycles = 4  -- this build's addition: float cycles per outer step of real = 'mixed'
 
 setmetatable(MultigridHIP, {
 	__call = function(cls, ...)
@@ -192,7 +207,7 @@ function MultigridHIP:makeOpts()
 	lib.mgp_opts_default(o)
 	o.dim = dim
 	o.n[0], o.n[1], o.n[2] = n, n, (dim == 3 and n or 1)
-	o.real_bytes = (b.real == 'float') and 4 or 8
+	o.real_bytes = (b.real == 'float' or b.real == 'mixed') and 4 or 8
 	o.nu1, o.nu2 = b.smooth, b.smooth
 	for field, map in pairs(CODES) do
 		if b[field] ~= nil then o[field] = assert(map[b[field]], 'unknown ' .. field) end
@@ -215,6 +230,8 @@ function MultigridHIP:createContext()
 		check(lib.mgp_create(pp, o), nil)
 		rawset(self, 'ctx', ffi.gc(pp[0], lib.mgp_destroy))
 		self:applyCoarse()
+		-- real = 'mixed': double psi / f around the float cycles (mgp_destroy frees them with the context)
+		if rawget(self, 'mixed') then check(lib.mgp_refine_begin(self.ctx), self.ctx) end
 	end
 end
 
@@ -254,13 +271,20 @@ function MultigridHIP:init(a, real, cpuDepth, engine)
 	else
 		-- cpu-raw.lua positional protocol: persistent coarse buffers (cpu-raw.lua:221) and, for
 		-- real = 'float', its LuaJIT-double arithmetic over float images (cpu-raw.lua:142-153)
-		args = {size = a, real = real, coarse_init = 'warm', arith = 'double'}
+		-- (real = 'mixed' refines cycles of gpu.lua's float arithmetic: arith = 'real')
+		args = {size = a, real = real, coarse_init = 'warm', arith = (real == 'mixed') and 'real' or 'double'}
 		rawset(self, 'cpuDepth', cpuDepth)
 		rawset(self, 'engine', engine)
 	end
 	local n = assert(tonumber(args.size), 'size is required')
 	local dim = args.dim or 2
 	rawset(self, 'real', args.real or 'double')
+	rawset(self, 'mixed', args.real == 'mixed')
+	if args.real == 'mixed' then
+		if args.arith == 'double' then error("real = 'mixed': arith = 'double' is not offered", 2) end
+		if args.ngpu and args.ngpu > 1 then error("real = 'mixed': one GPU only", 2) end
+		if args.innerCycles then rawset(self, 'innerCycles', args.innerCycles) end
+	end
 	rawset(self, 'dim', dim)
 	rawset(self, 'n', n)
 	-- cpu.lua:178 self.size = matrix{size, size}; cpu-raw.lua:146 self.size = size
@@ -279,8 +303,10 @@ function MultigridHIP:init(a, real, cpuDepth, engine)
 		arith = args.arith, device = args.device})
 	local cells = n * n * (dim == 3 and n or 1)
 	rawset(self, 'count', cells)
-	rawset(self, 'ctype', (rawget(self, 'real') == 'float') and 'float[?]' or 'double[?]')
-	rawset(self, 'ptype', (rawget(self, 'real') == 'float') and 'float*' or 'double*')
+	-- the context's real (real = 'mixed': a float context; its double psi / f are handled in get / setBuffer)
+	local f32 = rawget(self, 'real') == 'float' or rawget(self, 'mixed')
+	rawset(self, 'ctype', f32 and 'float[?]' or 'double[?]')
+	rawset(self, 'ptype', f32 and 'float*' or 'double*')
 	self:createContext()
 	self:initPointCharge()
 end
@@ -343,9 +369,22 @@ function MultigridHIP:residualNorm(level)
 	return r[0], f[0]
 end
 
+-- real = 'mixed': ||f - A psi||, ||f|| of the double fields
+function MultigridHIP:refineResidual()
+	local r, f = ffi.new('double[1]'), ffi.new('double[1]')
+	check(lib.mgp_refine_residual(self.ctx, r, f), self.ctx)
+	return r[0], f[0]
+end
+
 function MultigridHIP:getBuffer(which, level)
 	level = level or 0
 	local count = self.count
+	if rawget(self, 'mixed') and level == 0 and which <= 1 then
+		-- psi / f of real = 'mixed' are the double fields (MGP_REFINE_PSI = 0, MGP_REFINE_F = 1)
+		local buf = ffi.new('double[?]', count)
+		check(lib.mgp_refine_get(self.ctx, which, buf, count, 0), self.ctx)
+		return buf, count
+	end
 	if level ~= 0 then
 		-- a group's fields are the global box: nz_global (info[2]); one context's are its planes (info[3])
 		local info = ffi.new('int64_t[8]')
@@ -361,6 +400,10 @@ function MultigridHIP:getBuffer(which, level)
 end
 
 function MultigridHIP:setBuffer(which, buf)
+	if rawget(self, 'mixed') then
+		check(lib.mgp_refine_set(self.ctx, which, buf, self.count, 0), self.ctx)
+		return
+	end
 	local g = rawget(self, 'group')
 	if g then checkGroup(lib.mgp_group_set_field(g, 0, which, buf, self.count, 0), g)
 	else check(lib.mgp_set_field(self.ctx, 0, which, buf, self.count, 0), self.ctx) end
@@ -393,7 +436,9 @@ function MultigridHIP:step()
 	self:applyKnobs()
 	local err = ffi.new('double[1]')
 	local g = rawget(self, 'group')
-	if g then checkGroup(lib.mgp_group_cycle(g, err), g)
+	if rawget(self, 'mixed') then
+		check(lib.mgp_refine_step(self.ctx, self.innerCycles, nil, nil, err), self.ctx)
+	elseif g then checkGroup(lib.mgp_group_cycle(g, err), g)
 	else check(lib.mgp_cycle(self.ctx, err), self.ctx) end
 	if self.debug then print('err', err[0]) end
 	return err[0]
@@ -426,6 +471,7 @@ end
 -- cpu.lua:70 twoGrid(h, u, f) on lua-matrix-style tables u[i][j] (x = i; u updated in place)
 function MultigridHIP:twoGrid(h, u, f, L)
 	self:applyKnobs()
+	if rawget(self, 'mixed') then error("twoGrid: not offered with real = 'mixed' (level 0 is the refinement's scratch)", 2) end
 	if type(u) == 'table' then
 		local n = #u
 		local ub, fb = ffi.new(self.ctype, n * n), ffi.new(self.ctype, n * n)

@@ -51,8 +51,12 @@ MEM_HOST, MEM_DEVICE = 0, 1
 COARSE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                              ctypes.c_int64)
 TIMING_HALF_SWEEP, TIMING_FUSED_PRE, TIMING_FUSED_POST, TIMING_EXCHANGE, TIMING_COLLECTIVE = 0, 1, 2, 3, 4
+TIMING_REFINE_DEFECT, TIMING_REFINE_ADD = 5, 6
 TIMING_KINDS = {TIMING_HALF_SWEEP: "half_sweep", TIMING_FUSED_PRE: "fused_pre", TIMING_FUSED_POST: "fused_post",
-                TIMING_EXCHANGE: "exchange", TIMING_COLLECTIVE: "collective"}
+                TIMING_EXCHANGE: "exchange", TIMING_COLLECTIVE: "collective", TIMING_REFINE_DEFECT: "refine_defect",
+                TIMING_REFINE_ADD: "refine_add"}
+# the fp64 fields of mixed-precision refinement (mgp_refine_set / mgp_refine_get)
+REFINE_PSI, REFINE_F = 0, 1
 COMM_OPS = {0: "exchange", 1: "allgather", 2: "allreduce"}
 COMM_ID_BYTES = 128
 
@@ -116,6 +120,13 @@ SIGNATURES = {
     "mgp_metrics": (ctypes.c_int, [_vp, _P(_dbl), _P(_i64), _P(_dbl)]),
     "mgp_set_coarse_level": (ctypes.c_int, [_vp, _i64]),
     "mgp_residual_norm": (ctypes.c_int, [_vp, ctypes.c_int, _P(_dbl), _P(_dbl)]),
+    "mgp_refine_begin": (ctypes.c_int, [_vp]),
+    "mgp_refine_end": (ctypes.c_int, [_vp]),
+    "mgp_refine_set": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, ctypes.c_int]),
+    "mgp_refine_get": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, ctypes.c_int]),
+    "mgp_refine_residual": (ctypes.c_int, [_vp, _P(_dbl), _P(_dbl)]),
+    "mgp_refine_step": (ctypes.c_int, [_vp, _i32, _P(_dbl), _P(_dbl), _P(_dbl)]),
+    "mgp_refine_solve": (ctypes.c_int, [_vp, _i32, _dbl, _dbl, _i32, _P(_i32), _P(_dbl), _P(_dbl)]),
     "mgp_cg_solve": (ctypes.c_int, [_vp, _dbl, _i32, _vp, ctypes.c_int, _P(_i32), _P(_dbl), _P(_dbl)]),
     "mgp_set_coarse_handoff": (ctypes.c_int, [_vp, _i64, COARSE_FN, _vp]),
     "mgp_timing": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -250,6 +250,52 @@ class Context:
         self._chk(L.lib.mgp_residual_norm(self._h, level, ctypes.byref(r), ctypes.byref(f)))
         return r.value, f.value
 
+    # -- mixed-precision defect correction (mgp_refine_*): fp64 psi / f around the fp32 cycles --
+    def refine_begin(self):
+        """Start refinement on a real='float' context: fp64 psi / f = the widened level-0 u / f."""
+        self._chk(L.lib.mgp_refine_begin(self._h))
+
+    def refine_end(self):
+        """Narrow the fp64 psi / f into level 0's u / f and free them: an ordinary fp32 context again."""
+        self._chk(L.lib.mgp_refine_end(self._h))
+
+    def refine_set(self, which, arr):
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        self._chk(L.lib.mgp_refine_set(self._h, int(which), a.ctypes.data, a.size, L.MEM_HOST))
+
+    def refine_get(self, which):
+        """The fp64 psi (REFINE_PSI) or f (REFINE_F), shaped like get_psi()."""
+        out = np.empty(self.shape(0), dtype=np.float64)
+        self._chk(L.lib.mgp_refine_get(self._h, int(which), out.ctypes.data, out.size, L.MEM_HOST))
+        return out
+
+    def refine_residual(self):
+        """(||f - A psi||_2, ||f||_2) of the fp64 fields; psi is not changed."""
+        r, f = ctypes.c_double(), ctypes.c_double()
+        self._chk(L.lib.mgp_refine_residual(self._h, ctypes.byref(r), ctypes.byref(f)))
+        return r.value, f.value
+
+    def refine_step(self, inner=4):
+        """One outer step (fp64 defect, `inner` fp32 cycles from a zero guess, fp64 add): (rnorm, fnorm, err), the
+        norms those of the defect before this step's correction, err = sqrt(sum e^2 / N)."""
+        r, f, e = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        self._chk(L.lib.mgp_refine_step(self._h, int(inner), ctypes.byref(r), ctypes.byref(f), ctypes.byref(e)))
+        return r.value, f.value, e.value
+
+    def refine_solve(self, inner=4, rtol=0.0, epsilon=1e-10, maxouter=100):
+        """Outer steps until rnorm <= rtol * fnorm, err < epsilon, a non-finite value or maxouter steps:
+        (steps, rel_hist, err_hist) with rel_hist = rnorm / fnorm of every defect computed, err_hist each step's err."""
+        n = ctypes.c_int32()
+        rel = np.full(int(maxouter) + 1, np.nan)
+        err = np.full(max(int(maxouter), 1), np.nan)
+        pd = ctypes.POINTER(ctypes.c_double)
+        self._chk(L.lib.mgp_refine_solve(self._h, int(inner), float(rtol), float(epsilon), int(maxouter), ctypes.byref(n),
+                                         rel.ctypes.data_as(pd), err.ctypes.data_as(pd)))
+        k = n.value
+        # a step that ended the loop by its err (cpu.lua:214) is not followed by another defect
+        by_err = k > 0 and (err[k - 1] < epsilon or not np.isfinite(err[k - 1]))
+        return k, rel[:k if by_err else k + 1], err[:k]
+
     def cg_solve(self, epsilon=1e-20, maxiter=10000, history=False):
         """Device CG on the finest level (converge-multigrid-vs-krylov.lua:38-69): x0 = -f, b = f, stop at
         rSq / bSq < epsilon.  Returns (x, iterations, rSq / bSq[, |x|_inf per iteration])."""

@@ -12,6 +12,9 @@ the LuaJIT-FFI module a Lua user would load is lua/multigrid-poisson/hip.lua (IN
   ``:twoGrid(h, uPtr, fPtr, L)`` (cpu-raw.lua:142, 186, 239-258; gpu.lua:26, 296, 348).
   ``real='float'`` follows cpu-raw.lua's arithmetic by default (float buffers, every expression in
   double: ``arith='double'``); ``arith='real'`` gives gpu.lua's float-rounded OpenCL arithmetic.
+
+Both accept ``real='mixed'`` (this build's addition): fp64 ``psi`` / ``f`` and the double solver's outer loop
+(cpu.lua:196-216) around ``innerCycles`` fp32 cycles per step — mixed-precision defect correction, mgp_refine_*.
 """
 from __future__ import annotations
 
@@ -106,9 +109,14 @@ class MultigridHIP(_RawFields):
     ``real``, ``smoother``, ``cycle``, ``prolong``, ``coarse_init``, ``coarse_bc``, ``restriction``)
     default to the reference configuration: 2D, double, Jacobi 7+7, V-cycle, injection, 2x2 average,
     fresh zero guess.
+
+    ``real='mixed'`` (this build's addition): ``psi`` / ``f`` are float64, and ``step()`` is one step of
+    mixed-precision defect correction (the fp64 defect, ``innerCycles`` fp32 cycles on it from a zero guess, the fp64
+    add; mgp_refine_step) returning the double solver's err; ``twoGrid`` raises :class:`MGPError`.
     """
 
     debug = False
+    innerCycles = 4  # this build's addition: fp32 cycles per outer step of real='mixed' (no reference counterpart)
     smooth = 7  # cpu.lua:20
     epsilon = 1e-10  # cpu.lua:21
     maxiter = 1000  # cpu.lua:22
@@ -166,37 +174,52 @@ class MultigridHIP(_RawFields):
             return
         psi = f = None
         if self._ctx is not None:
-            psi, f = self._ctx.get_psi(), self._ctx.get_f()
+            psi, f = self.psi, self.f  # (fp64 for real='mixed')
             self._ctx.close()
         n = self.size[0]
-        opts = make_opts(n=(n, n, n if self.dim == 3 else 1), nu1=self.smooth, nu2=self.smooth, **self._build)
+        build = dict(self._build, real="float") if self.mixed else self._build
+        opts = make_opts(n=(n, n, n if self.dim == 3 else 1), nu1=self.smooth, nu2=self.smooth, **build)
         self._ctx = Context(opts)
         self._ctx_smooth = self.smooth
+        if self.mixed:
+            self._ctx.refine_begin()
         if psi is not None:
-            self._ctx.set_psi(psi)
-            self._ctx.set_f(f)
+            self.psi = psi
+            self.f = f
+
+    @property
+    def mixed(self) -> bool:
+        """real='mixed': fp64 psi / f refined by fp32 cycles."""
+        return self._build["real"] == "mixed"
 
     @property
     def psi(self) -> np.ndarray:
         """Current solution as an (n, n[, n]) host array (downloaded from HBM)."""
-        return self._ctx.get_psi()
+        return self._ctx.refine_get(L.REFINE_PSI) if self.mixed else self._ctx.get_psi()
 
     @psi.setter
     def psi(self, value):
-        self._ctx.set_psi(value)
+        if self.mixed:
+            self._ctx.refine_set(L.REFINE_PSI, value)
+        else:
+            self._ctx.set_psi(value)
 
     @property
     def f(self) -> np.ndarray:
-        return self._ctx.get_f()
+        return self._ctx.refine_get(L.REFINE_F) if self.mixed else self._ctx.get_f()
 
     @f.setter
     def f(self, value):
-        self._ctx.set_f(value)
+        if self.mixed:
+            self._ctx.refine_set(L.REFINE_F, value)
+        else:
+            self._ctx.set_f(value)
 
     def step(self) -> float:
-        """cpu.lua:196-206: psiOld = psi; twoGrid(1/n, psi, f); return RMS(psi - psiOld)."""
+        """cpu.lua:196-206: psiOld = psi; twoGrid(1/n, psi, f); return RMS(psi - psiOld).  real='mixed': one
+        refinement step of innerCycles fp32 cycles; the same err, of the fp64 psi."""
         self._ensure_ctx()
-        err = self._ctx.cycle()
+        err = self._ctx.refine_step(self.innerCycles)[2] if self.mixed else self._ctx.cycle()
         if self.debug:
             print("err", err)
         return err
@@ -247,9 +270,13 @@ class MultigridHIPRaw(_RawFields):
     takes host numpy arrays or integer device pointers (``mem=MEM_DEVICE``).  With ``real='float'`` the
     arithmetic is cpu-raw.lua's (LuaJIT doubles over float images: ``arith='double'``, the default of this
     protocol); ``arith='real'`` selects gpu.lua's (every operation rounded to float, gpu.lua:32).
+    ``real='mixed'`` (this build's addition): float64 ``psi`` / ``f`` refined by ``innerCycles`` fp32 cycles per
+    outer iteration (mgp_refine_step); the inner arithmetic is gpu.lua's (``arith`` is forced to ``'real'``, an
+    explicit ``arith='double'`` raises ValueError).
     """
 
     debugging = False
+    innerCycles = 4  # this build's addition: fp32 cycles per outer iteration of real='mixed'
     smooth = 7  # cpu-raw.lua:123
     accuracy = 1e-10  # cpu-raw.lua:124
 
@@ -259,8 +286,14 @@ class MultigridHIPRaw(_RawFields):
         self.cpuDepth = cpuDepth
         dim = int(build.pop("dim", 2))
         n = self.size
+        self.mixed = self.real == "mixed"
+        if self.mixed:
+            if build.get("arith") == "double":
+                raise ValueError("real='mixed' refines cycles of gpu.lua's float arithmetic: arith='double' is not offered")
+            build["arith"] = "real"
         self.arith = build.pop("arith", "double")  # cpu-raw.lua's LuaJIT arithmetic (no effect on double)
-        opts = make_opts(dim=dim, n=(n, n, n if dim == 3 else 1), real=self.real, nu1=build.pop("nu1", self.smooth),
+        opts = make_opts(dim=dim, n=(n, n, n if dim == 3 else 1), real="float" if self.mixed else self.real,
+                         nu1=build.pop("nu1", self.smooth),
                          nu2=build.pop("nu2", self.smooth), coarse_init=build.pop("coarse_init", "warm"),
                          arith=self.arith, **build)
         self._ctx = Context(opts)
@@ -269,6 +302,8 @@ class MultigridHIPRaw(_RawFields):
                 self._ctx.set_coarse_level(1 << int(cpuDepth))
             except MGPError as e:  # the default switch stays (cpu-raw arithmetic has no coarse engine)
                 log.info("cpuDepth %s not applied: %s", cpuDepth, e)
+        if self.mixed:
+            self._ctx.refine_begin()
         self._ctx.init_point_charge()  # call2D(initCells) (cpu-raw.lua:173)
         self.quiet = False
 
@@ -278,11 +313,11 @@ class MultigridHIPRaw(_RawFields):
 
     @property
     def psi(self):
-        return self._ctx.get_psi()
+        return self._ctx.refine_get(L.REFINE_PSI) if self.mixed else self._ctx.get_psi()
 
     @property
     def f(self):
-        return self._ctx.get_f()
+        return self._ctx.refine_get(L.REFINE_F) if self.mixed else self._ctx.get_f()
 
     def twoGrid(self, h, u, f, L_, mem=None):
         if isinstance(u, np.ndarray):
@@ -299,7 +334,7 @@ class MultigridHIPRaw(_RawFields):
             print("#iter", "err")
         errs = []
         for it in range(1, iters + 1):
-            err = self._ctx.cycle()
+            err = self._ctx.refine_step(self.innerCycles)[2] if self.mixed else self._ctx.cycle()
             errs.append(err)
             if not self.quiet:
                 print(it, err)
