@@ -285,6 +285,52 @@ int         mgp_group_get_field(mgp_group* g, int level, int which, void* dst, i
 int         mgp_group_residual_norm(mgp_group* g, int level, double* rnorm, double* fnorm);
 int         mgp_group_field_stats(mgp_group* g, int level, int which, uint64_t* hash, double stats[3]);
 
+/* Batched solves (build-defined; the reference solves one box): B independent members of ONE shape in one
+ * hierarchy on one GPU.  Every kernel of a cycle covers all members in one launch (the launches per cycle do not
+ * depend on B), and in mgp_batch_solve each member stops on its own.  Per member the cycle and the outer loop are
+ * the ordinary context's (cpu.lua:70-165, 196-216): a member's psi equals mgp_cycles' bit for bit.  The levels of
+ * <= 4096 cells run as one launch with one workgroup per member from LDS (engine 1), the levels above one launch
+ * per piece (engine 0).  A batch owns one stream and replays ONE captured cycle (MGP_GRAPH=0: eager launches,
+ * identical results); it is not thread-safe.
+ * Options (`o` describes one member): dim 2 / 3, power-of-two axes, real_bytes 4 / 8 with MGP_ARITH_REAL, MGP_JACOBI
+ * or MGP_RBGS, V / F, both prolongations, fresh / warm, both coarse boundaries, coarse_sweeps, err_mode 0 / 1.
+ * MGP_ERR_ARG naming the field, before any device call: batch < 1, world != 1, MGP_GS_LEX, MGP_ARITH_DOUBLE,
+ * MGP_RESTRICT_FULL_WEIGHTING, a member (n) of more than 2^24 level-0 cells (one such box fills the GPU: use
+ * mgp_create), batch * cells >= 2^31.  MGP_ERR_OOM leaves nothing allocated.
+ * Measured (tools/batch_time.py, profiles/batch_time.json): README "Many small boxes at once". */
+typedef struct mgp_batch mgp_batch;
+int         mgp_batch_create(mgp_batch** out, const mgp_opts* o, int32_t batch);
+void        mgp_batch_destroy(mgp_batch* b);
+/* The message of the last failed call on b; b == NULL: of the failed mgp_batch_create / mgp_batch_plan. */
+const char* mgp_batch_last_error(const mgp_batch* b);
+int         mgp_batch_size(const mgp_batch* b);
+/* The member hierarchy without a device (host logic only), validated like mgp_batch_create: up to max_levels rows
+ * of 8 int64 in mgp_plan's columns {nx, ny, nz, nz, 0, 0, engine, 0}, engine 0 = one launch per piece, 1 = the
+ * LDS engine.  Returns the number of levels; the rows do not depend on batch. */
+int         mgp_batch_plan(const mgp_opts* o, int32_t batch, int64_t* rows, int max_levels);
+/* mgp_init_point_charge on every member. */
+int         mgp_batch_init_point_charge(mgp_batch* b);
+/* Copy a level's field in / out.  member >= 0: one member, count = the level's cells; member == -1: all members,
+ * count = B * cells, member slowest, then x fastest as everywhere.  which: MGP_FIELD_U / MGP_FIELD_F on any level;
+ * on level 0 also MGP_FIELD_PSI_OLD (get only, err_mode 1; MGP_ERR_STATE otherwise).  mem: MGP_MEM_HOST |
+ * MGP_MEM_DEVICE (e.g. a PyTorch tensor's data_ptr()). */
+int         mgp_batch_set_field(mgp_batch* b, int member, int level, int which, const void* src, int64_t count, int mem);
+int         mgp_batch_get_field(const mgp_batch* b, int member, int level, int which, void* dst, int64_t count, int mem);
+/* k outer iterations (mgp_cycles) of EVERY member with one host synchronisation (one per 2^20 / B cycles);
+ * errs (may be NULL): k * B doubles, errs[it * B + m] (NaN with err_mode 0). */
+int         mgp_batch_cycles(mgp_batch* b, int32_t k, double* errs);
+/* MultigridCPU:solve() (cpu.lua:208-216) per member: member m stops after the first iteration whose err < epsilon
+ * or is not finite, or after maxiter; a stopped member's fields are not touched again (every kernel of the later
+ * cycles returns at once for it).  The stop state lives on the device; the host enqueues cycles in chunks that
+ * never pass maxiter and reads the number of active members after each.  iters[B], last_err[B] (either may be
+ * NULL).  MGP_ERR_STATE with err_mode 0. */
+int         mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iters, double* last_err);
+/* Per member mgp_residual_norm of level 0: rnorm[m] = ||f - A u||_2, fnorm[m] = ||f||_2 (fp64 sums: per wave,
+ * per workgroup, then in a fixed order); either may be NULL. */
+int         mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm);
+/* Kernel launches (graph nodes included) one cycle of the last mgp_batch_cycles / mgp_batch_solve enqueued. */
+int         mgp_batch_launches(const mgp_batch* b, int64_t* per_cycle);
+
 /* The reference's debugging check (MultigridCPURaw.debugging / MultigridGPU.debugging: show / showAndCheck after
  * every sweep and piece of twoGrid, error "found a nan" on a non-finite cell; cpu-raw.lua:126-140,
  * gpu.lua:269-284).  mode 1: every phase of every cycle (pre-smoothing, the restricted residual, the coarse solve

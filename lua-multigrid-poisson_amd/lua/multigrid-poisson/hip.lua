@@ -113,6 +113,19 @@ int         mgp_group_cycles(mgp_group* g, int32_t k, double* errs);
 int         mgp_group_set_field(mgp_group* g, int level, int which, const void* src, int64_t count, int mem);
 int         mgp_group_get_field(mgp_group* g, int level, int which, void* dst, int64_t count, int mem);
 int         mgp_group_residual_norm(mgp_group* g, int level, double* rnorm, double* fnorm);
+typedef struct mgp_batch mgp_batch;
+int         mgp_batch_create(mgp_batch** out, const mgp_opts* o, int32_t batch);
+void        mgp_batch_destroy(mgp_batch* b);
+const char* mgp_batch_last_error(const mgp_batch* b);
+int         mgp_batch_size(const mgp_batch* b);
+int         mgp_batch_plan(const mgp_opts* o, int32_t batch, int64_t* rows, int max_levels);
+int         mgp_batch_init_point_charge(mgp_batch* b);
+int         mgp_batch_set_field(mgp_batch* b, int member, int level, int which, const void* src, int64_t count, int mem);
+int         mgp_batch_get_field(const mgp_batch* b, int member, int level, int which, void* dst, int64_t count, int mem);
+int         mgp_batch_cycles(mgp_batch* b, int32_t k, double* errs);
+int         mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iters, double* last_err);
+int         mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm);
+int         mgp_batch_launches(const mgp_batch* b, int64_t* per_cycle);
 ]]
 
 local lib = ffi.load(os.getenv('MGP_LIBRARY') or 'mgpoisson')
@@ -489,5 +502,87 @@ function MultigridHIP:twoGrid(h, u, f, L)
 	end
 	check(lib.mgp_two_grid(self.ctx, h, u, f, L, 0), self.ctx)
 end
+
+-- MGBatch: `batch` independent boxes of one size in one hierarchy (mgp_batch_*; this build's addition, the reference
+-- solves one box).  MultigridHIP.Batch{size = n, batch = B, dim = ?, real = ?, smooth = ?, ...} takes the build
+-- fields of MultigridHIP's table protocol; every member starts as cpu.lua:180-193's point charge.  Buffers are raw
+-- real* of B * n^dim elements (member slowest, then x fastest), or of n^dim for one member (0-based).  errorCallback
+-- is not offered: the members stop on the device (cpu.lua:208-216 per member).  NOT EXECUTED here (no Lua runtime).
+local MGBatch = {}
+MGBatch.__index = MGBatch
+MGBatch.smooth = MultigridHIP.smooth
+MGBatch.epsilon = MultigridHIP.epsilon
+MGBatch.maxiter = MultigridHIP.maxiter
+
+local function checkBatch(rc, b)
+	if rc < 0 then error('libmgpoisson: ' .. ffi.string(lib.mgp_batch_last_error(b)), 3) end
+	return rc
+end
+
+setmetatable(MGBatch, {
+	__call = function(cls, a)
+		assert(a.errorCallback == nil, 'MGBatch: errorCallback is not offered (the members stop on the device)')
+		local self = setmetatable({}, cls)
+		self.n, self.dim, self.batch = assert(a.size), a.dim or 2, assert(a.batch)
+		if a.maxiter ~= nil then self.maxiter = a.maxiter end
+		if a.epsilon ~= nil then self.epsilon = a.epsilon end
+		self.build = {real = a.real or 'double', smooth = a.smooth or cls.smooth,
+			smoother = a.inPlaceIterativeSolver or a.smoother or 'jacobi', cycle = a.cycle, prolong = a.prolong,
+			coarse_init = a.coarse_init, coarse_bc = a.coarse_bc, device = a.device}
+		local o = MultigridHIP.makeOpts(self)
+		local out = ffi.new('mgp_batch*[1]')
+		checkBatch(lib.mgp_batch_create(out, o, self.batch), nil)
+		self.handle = ffi.gc(out[0], lib.mgp_batch_destroy)
+		self.ctype = o.real_bytes == 4 and 'float[?]' or 'double[?]'
+		self.cells = self.n ^ self.dim
+		self.iters = ffi.new('int32_t[?]', self.batch)
+		self.err = ffi.new('double[?]', self.batch)
+		self:initPointCharge()
+		return self
+	end,
+})
+
+function MGBatch:initPointCharge() checkBatch(lib.mgp_batch_init_point_charge(self.handle), self.handle) end
+
+-- which: 'psi' | 'f' | 'psiOld' (get only); member nil = every member
+function MGBatch:getBuffer(which, member, level)
+	local count = (member and 1 or self.batch) * (level and level > 0 and (self.n / 2 ^ level) ^ self.dim or self.cells)
+	local buf = ffi.new(self.ctype, count)
+	checkBatch(lib.mgp_batch_get_field(self.handle, member or -1, level or 0, FIELD[which], buf, count, 0), self.handle)
+	return buf, count
+end
+
+function MGBatch:setBuffer(which, buf, member, level, mem)
+	local count = (member and 1 or self.batch) * (level and level > 0 and (self.n / 2 ^ level) ^ self.dim or self.cells)
+	checkBatch(lib.mgp_batch_set_field(self.handle, member or -1, level or 0, FIELD[which], buf, count, mem or 0), self.handle)
+end
+
+-- cpu.lua:196-206 on every member, k times with one host synchronisation: errs[it * batch + m]
+function MGBatch:cycles(k)
+	local errs = ffi.new('double[?]', k * self.batch)
+	checkBatch(lib.mgp_batch_cycles(self.handle, k, errs), self.handle)
+	return errs
+end
+
+function MGBatch:step() return self:cycles(1) end
+
+-- cpu.lua:208-216 per member: fills self.iters[m] and self.err[m]
+function MGBatch:solve()
+	checkBatch(lib.mgp_batch_solve(self.handle, self.epsilon, self.maxiter, self.iters, self.err), self.handle)
+end
+
+function MGBatch:residualNorm()
+	local r, f = ffi.new('double[?]', self.batch), ffi.new('double[?]', self.batch)
+	checkBatch(lib.mgp_batch_residual_norm(self.handle, r, f), self.handle)
+	return r, f
+end
+
+function MGBatch:launches()
+	local n = ffi.new('int64_t[1]')
+	checkBatch(lib.mgp_batch_launches(self.handle, n), self.handle)
+	return tonumber(n[0])
+end
+
+MultigridHIP.Batch = MGBatch
 
 return MultigridHIP

@@ -148,6 +148,18 @@ SIGNATURES = {
     "mgp_group_get_field": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _i64, ctypes.c_int]),
     "mgp_group_residual_norm": (ctypes.c_int, [_vp, ctypes.c_int, _P(_dbl), _P(_dbl)]),
     "mgp_group_field_stats": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(ctypes.c_uint64), _P(_dbl)]),
+    "mgp_batch_create": (ctypes.c_int, [_P(_vp), _P(MGPOpts), _i32]),
+    "mgp_batch_destroy": (None, [_vp]),
+    "mgp_batch_last_error": (ctypes.c_char_p, [_vp]),
+    "mgp_batch_size": (ctypes.c_int, [_vp]),
+    "mgp_batch_plan": (ctypes.c_int, [_P(MGPOpts), _i32, _P(_i64), ctypes.c_int]),
+    "mgp_batch_init_point_charge": (ctypes.c_int, [_vp]),
+    "mgp_batch_set_field": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, ctypes.c_int]),
+    "mgp_batch_get_field": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _i64, ctypes.c_int]),
+    "mgp_batch_cycles": (ctypes.c_int, [_vp, _i32, _P(_dbl)]),
+    "mgp_batch_solve": (ctypes.c_int, [_vp, _dbl, _i32, _P(_i32), _P(_dbl)]),
+    "mgp_batch_residual_norm": (ctypes.c_int, [_vp, _P(_dbl), _P(_dbl)]),
+    "mgp_batch_launches": (ctypes.c_int, [_vp, _P(_i64)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():
@@ -178,6 +190,13 @@ def check_group(code: int, group=None) -> int:
     return code
 
 
+def check_batch(code: int, batch=None) -> int:
+    if code < 0:
+        msg = lib.mgp_batch_last_error(batch)
+        raise MGPError(code, msg.decode() if msg else "")
+    return code
+
+
 def default_opts() -> MGPOpts:
     o = MGPOpts()
     lib.mgp_opts_default(ctypes.byref(o))
@@ -200,6 +219,16 @@ def plan(opts: MGPOpts, max_levels: int = 48):
     for l, d in enumerate(out):
         d["engine"] = ("piece", "tail", "zs", "blk", "zpost")[rows[8 * l + 6]]
     return out
+
+
+def plan_batch(opts: MGPOpts, batch: int, max_levels: int = 48):
+    """Host-only level plan of one member of a batch (mgp_batch_plan, validated like BatchContext): list of dicts
+    (nx, ny, nz, engine), engine "piece" (one launch per piece, all members) or "tail" (the LDS engine, one
+    workgroup per member)."""
+    rows = (ctypes.c_int64 * (8 * max_levels))()
+    n = check_batch(lib.mgp_batch_plan(ctypes.byref(opts), int(batch), rows, max_levels))
+    return [dict(nx=rows[8 * l], ny=rows[8 * l + 1], nz=rows[8 * l + 2], engine=("piece", "tail")[rows[8 * l + 6]])
+            for l in range(n)]
 
 
 def plan_comm(opts: MGPOpts, cycles: int = 1, max_rows: int = 1 << 14):

@@ -434,3 +434,129 @@ class _RankView(Context):
 
     def close(self):
         self._h = None
+
+
+class BatchContext:
+    """Owns one mgp_batch: ``batch`` independent members of the shape ``opts`` describes, in one hierarchy.  Every
+    kernel of a cycle covers all members in one launch; in :meth:`solve` each member stops on its own.
+
+    Host arrays have shape (B, [nz,] ny, nx) for all members (``member=None``) or one member's shape; the ``*_ptr``
+    variants take an integer device pointer (e.g. ``torch_tensor.data_ptr()``) of the same layout.
+    """
+
+    def __init__(self, opts: L.MGPOpts, batch: int):
+        self.opts = opts
+        self.dtype = np.dtype(np.float64 if opts.real_bytes == 8 else np.float32)
+        h = ctypes.c_void_p()
+        L.check_batch(L.lib.mgp_batch_create(ctypes.byref(h), ctypes.byref(opts), int(batch)))
+        self._h = h
+        self.batch = int(L.lib.mgp_batch_size(h))
+        self.levels = L.plan_batch(opts, self.batch)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib.mgp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _chk(self, rc):
+        return L.check_batch(rc, self._h)
+
+    def member_shape(self, level=0):
+        lv = self.levels[level]
+        return (lv["nz"], lv["ny"], lv["nx"]) if self.opts.dim == 3 else (lv["ny"], lv["nx"])
+
+    def shape(self, member=None, level=0):
+        return ((self.batch,) if member is None else ()) + self.member_shape(level)
+
+    def init_point_charge(self):
+        self._chk(L.lib.mgp_batch_init_point_charge(self._h))
+
+    def set_field(self, which, arr, member=None, level=0):
+        a = np.ascontiguousarray(arr, dtype=self.dtype)
+        want = int(np.prod(self.shape(member, level)))
+        if a.size != want:
+            raise ValueError(f"expected {want} elements, got {a.size}")
+        self._chk(L.lib.mgp_batch_set_field(self._h, -1 if member is None else int(member), level, which, a.ctypes.data,
+                                            a.size, L.MEM_HOST))
+
+    def get_field(self, which, member=None, level=0):
+        out = np.empty(self.shape(member, level), dtype=self.dtype)
+        self._chk(L.lib.mgp_batch_get_field(self._h, -1 if member is None else int(member), level, which,
+                                            out.ctypes.data, out.size, L.MEM_HOST))
+        return out
+
+    def set_field_ptr(self, which, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        n = int(np.prod(self.shape(member, level)))
+        self._chk(L.lib.mgp_batch_set_field(self._h, -1 if member is None else int(member), level, which, int(ptr), n, mem))
+
+    def get_field_ptr(self, which, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        n = int(np.prod(self.shape(member, level)))
+        self._chk(L.lib.mgp_batch_get_field(self._h, -1 if member is None else int(member), level, which, int(ptr), n, mem))
+
+    def set_psi(self, arr, member=None, level=0):
+        self.set_field(L.FIELD_U, arr, member, level)
+
+    def set_f(self, arr, member=None, level=0):
+        self.set_field(L.FIELD_F, arr, member, level)
+
+    def get_psi(self, member=None, level=0):
+        return self.get_field(L.FIELD_U, member, level)
+
+    def get_f(self, member=None, level=0):
+        return self.get_field(L.FIELD_F, member, level)
+
+    def get_psi_old(self, member=None):
+        return self.get_field(L.FIELD_PSI_OLD, member, 0)
+
+    def set_psi_ptr(self, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        self.set_field_ptr(L.FIELD_U, ptr, member, level, mem)
+
+    def set_f_ptr(self, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        self.set_field_ptr(L.FIELD_F, ptr, member, level, mem)
+
+    def get_psi_ptr(self, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        self.get_field_ptr(L.FIELD_U, ptr, member, level, mem)
+
+    def get_f_ptr(self, ptr, member=None, level=0, mem=L.MEM_DEVICE):
+        self.get_field_ptr(L.FIELD_F, ptr, member, level, mem)
+
+    def cycles(self, k: int) -> np.ndarray:
+        """k outer iterations of every member with one host synchronisation; the (k, B) errs."""
+        errs = np.zeros((int(k), self.batch), dtype=np.float64)
+        self._chk(L.lib.mgp_batch_cycles(self._h, int(k), errs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return errs
+
+    def solve(self, epsilon: float, maxiter: int):
+        """cpu.lua:208-216 per member: (iters, last_err), each of B entries."""
+        iters = np.zeros(self.batch, dtype=np.int32)
+        errs = np.zeros(self.batch, dtype=np.float64)
+        self._chk(L.lib.mgp_batch_solve(self._h, float(epsilon), int(maxiter),
+                                        iters.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                        errs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return iters, errs
+
+    def residual_norm(self):
+        """Per member (||f - A u||_2, ||f||_2) of level 0: two arrays of B entries."""
+        r = np.zeros(self.batch, dtype=np.float64)
+        f = np.zeros(self.batch, dtype=np.float64)
+        self._chk(L.lib.mgp_batch_residual_norm(self._h, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return r, f
+
+    def launches(self) -> int:
+        """Kernel launches per cycle of the last cycles() / solve() call (independent of B)."""
+        n = ctypes.c_int64()
+        self._chk(L.lib.mgp_batch_launches(self._h, ctypes.byref(n)))
+        return n.value

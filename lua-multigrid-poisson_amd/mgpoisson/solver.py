@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import MGPError
-from .context import Context, make_opts
+from .context import BatchContext, Context, make_opts
 
 log = logging.getLogger(__name__)
 
@@ -249,6 +249,71 @@ class MultigridHIP(_RawFields):
         for i, row in enumerate(u):
             row[:] = ua[:, i].tolist()
         return u
+
+
+class MultigridHIPBatch:
+    """``batch`` independent ``MultigridHIP`` problems of one size in one hierarchy (mgp_batch_*; this build's
+    addition, the reference solves one box): ``MultigridHIPBatch(size=n, batch=B, ...)`` with MultigridHIP's build
+    keywords.  ``psi`` / ``f`` have shape (B, n, n[, n]); every member starts as cpu.lua:180-193's point charge.
+    ``step()`` returns the B errs of one outer iteration; ``solve()`` runs cpu.lua:208-216 per member on the device
+    and sets ``.iters`` / ``.err`` (B entries each).  ``errorCallback`` is not offered: a host callback per iteration
+    would bring back the synchronisation per cycle that batching removes.
+    """
+
+    smooth = MultigridHIP.smooth  # cpu.lua:20
+    epsilon = MultigridHIP.epsilon  # cpu.lua:21
+    maxiter = MultigridHIP.maxiter  # cpu.lua:22
+
+    def __init__(self, args=None, **kw):
+        a = dict(args or {})
+        a.update(kw)
+        if a.get("errorCallback") is not None:
+            raise TypeError("MultigridHIPBatch: errorCallback is not offered (the members stop on the device)")
+        if "size" not in a or "batch" not in a:
+            raise TypeError("MultigridHIPBatch: 'size' and 'batch' are required")
+        n = int(a["size"])
+        for k in ("maxiter", "epsilon"):
+            if a.get(k) is not None:
+                setattr(self, k, a[k])
+        if a.get("smooth") is not None:
+            self.smooth = int(a["smooth"])
+        self.dim = int(a.get("dim", 2))
+        self.size = (n,) * self.dim
+        self.batch = int(a["batch"])
+        sm = a.get("inPlaceIterativeSolver", a.get("smoother", "jacobi"))
+        opts = make_opts(n=(n, n, n if self.dim == 3 else 1), nu1=self.smooth, nu2=self.smooth, dim=self.dim,
+                         real=a.get("real", "double"), smoother=_smoother_name(sm), cycle=a.get("cycle", "V"),
+                         prolong=a.get("prolong", "pc"), coarse_init=a.get("coarse_init", "fresh"),
+                         coarse_bc=a.get("coarse_bc", "zero"), restriction=a.get("restriction", "average"),
+                         device=a.get("device", -1))
+        self.ctx = BatchContext(opts, self.batch)
+        self.ctx.init_point_charge()
+        self.iters = np.zeros(self.batch, dtype=np.int32)
+        self.err = np.full(self.batch, np.nan)
+
+    @property
+    def psi(self) -> np.ndarray:
+        return self.ctx.get_psi()
+
+    @psi.setter
+    def psi(self, value):
+        self.ctx.set_psi(value)
+
+    @property
+    def f(self) -> np.ndarray:
+        return self.ctx.get_f()
+
+    @f.setter
+    def f(self, value):
+        self.ctx.set_f(value)
+
+    def step(self) -> np.ndarray:
+        """cpu.lua:196-206 on every member: the B errs."""
+        return self.ctx.cycles(1)[0]
+
+    def solve(self):
+        """cpu.lua:208-216 per member, on the device."""
+        self.iters, self.err = self.ctx.solve(self.epsilon, int(self.maxiter))
 
 
 def _smoother_name(v):
