@@ -171,6 +171,7 @@ struct FusedTuning {
     int patch_pre = 0, patch_post = -1;
     bool fwf = true;     // MGP_ZS_FWF=0: the full weighting after the fused PRE instead of inside it
     int post_zc = 256;   // MGP_ZS_POST_ZC: POST's z-chunks hold at most this many planes (0: no limit)
+    bool split = true;   // MGP_ZS_SPLIT=0: fp32 cl = 0 PRE (2^3 average) on k_zs instead of the stage-split k_zs_split
     bool stamp_r = false;  // MGP_STAMP_R=1 (ZS_STAMP timing builds only): POST's wall-clock stamps go to level l+1's f
 };
 FusedTuning fused_tuning_from_env();

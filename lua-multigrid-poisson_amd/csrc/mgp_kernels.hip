@@ -1991,6 +1991,67 @@ constexpr bool kZsRask = ZS_RASK != 0;
 #ifndef ZS_WPE_POST
 #define ZS_WPE_POST 4
 #endif
+// Tile (tx, ty) of a launch's tile index; patch != 0: the tiles an XCD runs at once form px x py patches (host:
+// px | tiles_x, py | tiles_y; zs_patch)
+__device__ __forceinline__ void zs_tile_xy(int tile, int tiles_x, int patch, int& tx, int& ty)
+{
+    tx = tile % tiles_x;
+    ty = tile / tiles_x;
+    if (patch) {
+        const int px = patch & 255, py = patch >> 8, per = px * py, prow = tiles_x / px;
+        const int pi = tile / per, q = tile % per;
+        tx = (pi % prow) * px + q % px;
+        ty = (pi / prow) * py + q / px;
+    }
+}
+
+// PRE's 2^3-average restriction of one thread's residuals rr[x parity][e] of fine plane q (dq = q - Z0; the odd row's
+// residuals xr of plane q - 1 come from the row's partner through xw's other half, see k_zs): the odd rows hand
+// theirs to the even row, which sums the eight children in the reference order and stores R / 8 when the coarse
+// plane (q - 1) / 2 is complete.
+template <typename T, int N>
+__device__ __forceinline__ void zs_restrict_avg(const T (&rr)[2][N], const T (&xr)[2 * N], T (&acc)[N], int dq, int zc,
+                                                bool even_row, T* xw, T* __restrict__ R, int K, int J, int gm, int cz0,
+                                                const Geo& gc)
+{
+    if (!even_row) {
+        if (dq < zc) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                xw[e] = rr[0][e];
+                xw[N + e] = rr[1][e];
+            }
+        }
+    } else {
+        if (dq >= 1) {  // the odd row's children of plane q - 1
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                acc[e] = acc[e] + xr[e];
+                acc[e] = acc[e] + xr[N + e];
+            }
+            if ((dq & 1) == 0) {  // coarse plane (q - 1) / 2 complete (K, J: global)
+                T* rowc = R + (int64_t)(K - cz0) * gc.P + (int64_t)J * gc.hw;
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    const int I = gm + e;
+                    rowc[((I + J + K) & 1) * gc.H + (I >> 1)] = (T)0.125 * acc[e];
+                }
+            }
+        }
+        if (dq < zc) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                if ((dq & 1) == 0) {
+                    acc[e] = rr[0][e] + rr[1][e];
+                } else {
+                    acc[e] = acc[e] + rr[0][e];
+                    acc[e] = acc[e] + rr[1][e];
+                }
+            }
+        }
+    }
+}
+
 template <typename T, bool PRE, int LINEAR, bool ERR, bool CLZ, bool WIDE = false>
 __global__ __launch_bounds__((ZsShape<T, PRE, CLZ, WIDE, PRE && LINEAR == 2>::NTL))
 __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_zs(const T* __restrict__ src, const T* __restrict__ f,
@@ -2022,13 +2083,8 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     const int b = xcd_remap(blockIdx.x, gridDim.x);
     const int tile = b % (tiles_x * tiles_y);
     const int Z0 = (b / (tiles_x * tiles_y)) * zc;
-    int tx_ = tile % tiles_x, ty_ = tile / tiles_x;
-    if (patch) {  // the tiles an XCD runs at once form px x py patches (host: px | tiles_x, py | tiles_y)
-        const int px = patch & 255, py = patch >> 8, per = px * py, prow = tiles_x / px;
-        const int pi = tile / per, q = tile % per;
-        tx_ = (pi % prow) * px + q % px;
-        ty_ = (pi / prow) * py + q / px;
-    }
+    int tx_, ty_;
+    zs_tile_xy(tile, tiles_x, patch, tx_, ty_);
     const int X0 = tx_ * TX, Y0 = ty_ * TY;
     const int hw = g.hw, Hh = (int)g.H;
     const int z0 = (int)g.z0, gnz = (int)g.gnz, cz0 = (int)gc.z0;
@@ -2390,46 +2446,8 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
                 rr[1][e] = pq == 0 ? rblk[e] : rred[e];
             }
             const int dq = q - (ST ? (Z0 & ~1) : Z0);
-            if (dq >= 0 && dq <= zc && tile_xy) {
-                if (!even_row) {
-                    if (dq < zc) {
-                        T* x = xs(q);
-#pragma unroll
-                        for (int e = 0; e < N; ++e) {
-                            x[e] = rr[0][e];
-                            x[N + e] = rr[1][e];
-                        }
-                    }
-                } else {
-                    if (dq >= 1) {  // the odd row's children of plane q - 1
-#pragma unroll
-                        for (int e = 0; e < N; ++e) {
-                            acc[e] = acc[e] + xr[e];
-                            acc[e] = acc[e] + xr[N + e];
-                        }
-                        if ((dq & 1) == 0) {  // coarse plane (q - 1) / 2 complete
-                            const int K = (zz0 + q - 1) >> 1, J = gy >> 1;  // global
-                            T* rowc = R + (int64_t)(K - cz0) * gc.P + (int64_t)J * gc.hw;
-#pragma unroll
-                            for (int e = 0; e < N; ++e) {
-                                const int I = col.gm + e;
-                                rowc[((I + J + K) & 1) * gc.H + (I >> 1)] = (T)0.125 * acc[e];
-                            }
-                        }
-                    }
-                    if (dq < zc) {
-#pragma unroll
-                        for (int e = 0; e < N; ++e) {
-                            if ((dq & 1) == 0) {
-                                acc[e] = rr[0][e] + rr[1][e];
-                            } else {
-                                acc[e] = acc[e] + rr[0][e];
-                                acc[e] = acc[e] + rr[1][e];
-                            }
-                        }
-                    }
-                }
-            }
+            if (dq >= 0 && dq <= zc && tile_xy)
+                zs_restrict_avg<T, N>(rr, xr, acc, dq, zc, even_row, xs(q), R, (zz0 + q - 1) >> 1, gy >> 1, col.gm, cz0, gc);
         }
         // ---- PRE, FWF: residual of plane p - 5 into RX, the x-combination of plane p - 6, the y-combination and the
         // coarse planes of plane p - 7 (fw_eval's order; cells outside the box weigh 0) ----
@@ -2617,6 +2635,326 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     }
     for (; p <= p_end; p += UNR) group(GEN, RPL, RO0, p, p_end);
     if constexpr (ERR && !PRE) block_partial_t<NTL>(err + err1, partials);  // (PRE: ERR is ZSRC, no partials)
+}
+
+// ---- k_zs PRE with its stages split over two groups of waves (fp32, cl = 0, the 2^3-average restriction) ----
+//
+// k_zs's step is a chain: stage k's newest z-neighbour is the plane stage k - 1 computed in the same step, so the
+// tile wave that sits alone on its SIMD runs stage 0, four half-sweeps and the residual back to back, with nothing
+// to cover its LDS round trips.  Here two groups of waves share the chain:
+//   group A  stage 0 (the prefetched black u and f) and stages 1 .. 3: at step p planes p .. p - 3, as k_zs
+//   group B  stage 4, the store of the smoothed black plane and the residual + restriction, one step behind:
+//            at step p planes p - 5, p - 5 and p - 6
+// The hand-off is stage 3's output, which k_zs already leaves in a 4-slot LDS ring for stage 4's in-plane neighbours:
+// B reads the newest plane of its own column from it (plane p - 4, written one step earlier) into its register ring
+// W3, so k_zs's slots keep their layout and the step keeps its single barrier..  Stage 4 needs the black cells of stage
+// 2 nowhere (a Gauss-Seidel update does not read the value it replaces), so no u crosses otherwise..  A leaves the f of
+// B's planes in two LDS rings of their own (red f of plane p - 3, black f of plane p - 2, both in its registers
+// anyway), so B issues no global load: fetching those lines a second time, three and four steps after A, cost more
+// than the split gained (PRE 416 against 317 us at 512^3)..  A's threads are k_zs's (the full H = 5 trapezoid, the same
+// wave roles); B's cover the rows within 1 of the tile..  The 20 threads of B's two halo rows share a wave with the 40
+// of A's rows d >= 4 (both run one light stage), which keeps the workgroup at 12 waves: three on a SIMD, 168
+// VGPRs..  Every expression is k_zs's, in its order: the results are bit-identical. The warm-up and the drain of a chunk
+// grow by one step; the planes read from HBM (and the ghost planes of a slab) do not change.
+template <typename T>
+struct ZsSplit {
+    using S = ZsShape<T, true, true>;
+    static_assert(S::XPAIR && S::H == 5 && S::NS3 == 4 && kZsRask, "the split follows k_zs's 64 x 32 PRE layout");
+    static constexpr int NTW = S::TC / 64;  // tile waves of each group
+    // Wave order: A's tile waves, B's tile waves, A's x-halo wave, B's x-halo wave, A's rows d = 1..3, then the
+    // mixed wave (lanes [0, MA): A's rows d >= 4, lanes [MA, MA + MB): B's rows d = 1).  With waves dealt to the
+    // four SIMDs in turn, every SIMD gets one tile wave of each group and one halo wave.
+    static constexpr int NW = 2 * NTW + 4, NTL = 64 * NW, WMIX = NW - 1;
+    static constexpr int MA = S::YT2 - S::YT2S, MB = 2 * S::G;
+    static_assert(NTW == 4 && S::NTL == 64 * 7 && S::YT2S == 64 * 6 && S::YT0 == 64 * 5 && MA + MB <= 64, "wave order");
+    // wave w: 0 group A, 1 group B, 2 mixed; its wave index within the group's own thread numbering
+    static constexpr int wave_kind(int w) { return w == WMIX ? 2 : (w < 2 * NTW ? w >= NTW : ((w - 2 * NTW) & 1)); }
+    static constexpr int local_wave(int w) { return w < 2 * NTW ? w % NTW : NTW + (w - 2 * NTW) / 2; }
+    // B's thread t: the tile rows and their x-halo groups as k_zs's threads, then the rows d = 1
+    static constexpr int BT1 = S::YT0 + MB;
+    static __device__ __forceinline__ int b_yrow(int t)
+    {
+        if (t < S::YT0) return S::yrow(t);
+        if (t < BT1) return t - S::YT0 < S::G ? S::H - 1 : S::H + S::TY;
+        return -1;
+    }
+    static __device__ __forceinline__ int b_ycol(int t) { return t < S::YT0 ? S::ycol(t) : (t - S::YT0) % S::G; }
+    // LDS: k_zs's layout, then the f hand-off: rings of 4 planes of red f and of black f over B's rows
+    static constexpr int FROWS = S::TY + 2, FSLOT = FROWS * S::HWE;
+    static constexpr int OFFFR = (int)(S::lds_bytes / sizeof(T)), OFFFB = OFFFR + 4 * FSLOT;
+    static constexpr size_t lds_bytes = (size_t)(OFFFB + 4 * FSLOT) * sizeof(T);
+    // one workgroup per CU: <= 1024 threads, <= 160 KiB LDS, and at 12 waves (3 on a SIMD) <= 168 VGPRs, which the
+    // launch bound makes the compiler's limit
+    static_assert(NTL <= 1024 && NW <= 12, "too many waves for 168 VGPRs");
+    static_assert(lds_bytes <= 160 * 1024, "LDS");
+};
+
+template <typename T, bool ZSRC>
+__global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restrict__ src, const T* __restrict__ f,
+                                                                 T* __restrict__ dst, T* __restrict__ R, Geo g, Geo gc,
+                                                                 Op<T, 3> op, int zc, int gz, int patch)
+{
+    using SP = ZsSplit<T>;
+    using S = typename SP::S;
+    constexpr int N = S::N, H = S::H, HWE = S::HWE, G = S::G, YE = S::YE, SLOT = S::SLOT, TX = S::TX, TY = S::TY,
+                  NS3 = S::NS3;
+    using VT = Vec<T, N>;
+    using PF = ZsPrefetch<T, N>;
+    constexpr int PFD = ZS_PFD_PRE, NPF = PFD + 1, UNR = NPF == 3 ? 12 : 4;
+    static_assert(PFD >= 1 && PFD <= 3, "prefetch distance 1..3");
+    extern __shared__ __align__(16) unsigned char zs_smem[];
+    T* const lds = reinterpret_cast<T*>(zs_smem);
+    const int tid = threadIdx.x;
+
+    const int tiles_x = g.nx / TX, tiles_y = g.ny / TY;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile = b % (tiles_x * tiles_y);
+    const int Z0 = (b / (tiles_x * tiles_y)) * zc;
+    int tx_, ty_;
+    zs_tile_xy(tile, tiles_x, patch, tx_, ty_);
+    const int X0 = tx_ * TX, Y0 = ty_ * TY;
+    const int hw = g.hw, Hh = (int)g.H;
+    const int z0 = (int)g.z0, gnz = (int)g.gnz, cz0 = (int)gc.z0;
+    const int64_t P = g.P;
+    const int qlo = -gz, qhi = (int)g.nz - 1 + gz;  // readable local planes
+
+    // my wave's kind, my group, my thread of it and its column of the extended tile (as k_zs)
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int wk = SP::wave_kind(wv), lw = SP::local_wave(wv);
+    const bool grp_b = wk == 1 || (wk == 2 && lane >= SP::MA);
+    const int lt = wk == 2 ? (grp_b ? S::YT0 + lane - SP::MA : S::YT2S + lane) : 64 * lw + lane;
+    const int yr_ = grp_b ? SP::b_yrow(lt) : S::yrow(lt);
+    const bool on = yr_ >= 0;
+    const int gx = on ? (grp_b ? SP::b_ycol(lt) : S::ycol(lt)) : 0, ye = on ? yr_ : 0;
+    const int gy = Y0 - H + ye;
+    const int m0 = gx * N;
+    ZsCol col;
+    col.lrow = ye * HWE + m0;
+    col.lym = (ye > 0 ? ye - 1 : ye) * HWE + m0;
+    col.lyp = (ye < YE - 1 ? ye + 1 : ye) * HWE + m0;
+    col.gm = (X0 - S::HX) / 2 + m0;  // global packed m of my first cell
+    col.x_first = gx == 0;
+    col.x_last = gx == G - 1;
+    col.lxm = col.x_first ? col.lrow : col.lrow - N;
+    col.lxp = col.x_last ? col.lrow : col.lrow + N;
+    const bool in_xy = on && gy >= 0 && gy < g.ny && col.gm >= 0 && col.gm < hw;
+    col.xin = true;  // (cl = 0: unused)
+    // columns outside the box load from a clamped in-plane position; their results never reach LDS or HBM
+    const int cgy = gy < 0 ? 0 : (gy >= g.ny ? g.ny - 1 : gy);
+    const int cgm = col.gm < 0 ? 0 : (col.gm > hw - N ? hw - N : col.gm);
+    const int goff = cgy * hw + cgm;  // in-plane offset (nx * ny < 2^31)
+    const bool tile_xy = on && ye >= H && ye < H + TY && gx >= S::HXG && gx < G - S::HXG;
+    // my column in a slot of the f hand-off (B's rows: those within 1 of the tile)
+    const bool frow = on && ye >= H - 1 && ye <= H + TY;
+    const int lf = frow ? (ye - (H - 1)) * HWE + m0 : 0;
+    auto fslot = [&](int off, int q) { return lds + off + (q & 3) * SP::FSLOT + lf; };
+    const int zlo = Z0 - H;
+    const ZsDiag<T> dz = {};  // (cl = 0: unused)
+    const int p_end = Z0 + zc + 6;
+    auto inz = [&](int q) { return z0 + q >= 0 && z0 + q < gnz; };  // inside the global box
+    auto pcl = [&](int q) { return q < qlo ? qlo : (q > qhi ? qhi : q); };
+    auto slot = [&](int off, int ns, int q) { return lds + off + (q & (ns - 1)) * SLOT; };
+    const int rowpar = (gy + z0) & 1;
+    auto par = [&](int q) { return rowpar ^ (q & 1); };
+    const VT vz = vzero<T, N>();
+
+    for (int i = tid; i < (int)(SP::lds_bytes / sizeof(T)); i += SP::NTL) lds[i] = (T)0;
+    __syncthreads();
+
+    // steady steps [ps, pe], as k_zs: every plane a step touches (p .. p - 6) inside the box, the prefetched planes
+    // readable, whole groups of UNR steps, even z0 and Z0 (static plane parity)
+    int ps = zlo, pe = p_end;
+    ps = ps > 7 - z0 ? ps : 7 - z0;
+    ps = ps > qlo + 4 ? ps : qlo + 4;
+    pe = pe < gnz - 1 - z0 ? pe : gnz - 1 - z0;
+    pe = pe < qhi - PFD ? pe : qhi - PFD;
+    ps += (UNR - (ps - zlo) % UNR) % UNR;
+    pe -= (pe - ps + 1) % UNR;
+    if (pe < ps || ((z0 | Z0) & 1)) ps = pe = zlo - 1;
+    const std::false_type GEN;
+    const std::true_type STY;
+    // Every wave runs the same steps, whatever its kind, and each step ends in the step's one barrier: the bounds
+    // above are the workgroup's.  prefetch / step: the wave kind's.
+    auto run = [&](auto&& prefetch, auto&& step) __attribute__((always_inline)) {
+        PF pb[NPF];
+#pragma unroll
+        for (int k = 0; k < PFD; ++k) prefetch(GEN, pb[k], zlo + k);
+        int p = zlo;
+        auto group = [&](auto st, int p0, int plim) __attribute__((always_inline)) {
+            zs_unroll<UNR>([&](auto kk) __attribute__((always_inline)) {
+                constexpr int k = decltype(kk)::value;
+                if (k == 0 || p0 + k <= plim) {
+                    step(st, std::integral_constant<int, (k & 3)>(), pb[k % NPF], pb[(k + PFD) % NPF], p0 + k);
+                    lds_barrier();
+                }
+            });
+        };
+        for (; p < ps; p += UNR) group(GEN, p, p + UNR);
+        for (; p <= pe; p += UNR) group(STY, p, p + UNR);
+        for (; p <= p_end; p += UNR) group(GEN, p, p_end);
+    };
+
+    // ---- group A: stages 0 .. 3 (k_zs's, with its wave roles: rows d >= 4 run stage 1 only) ----
+    const T* const src_black = ZSRC ? nullptr : src + Hh;
+    auto prefetch_a = [&](auto st, PF& r, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        if (ST) {
+            const int64_t pP = (int64_t)p * P;
+            if constexpr (ZSRC)
+                r.u = vzero<T, N>();
+            else
+                r.u = gload<T, N, kZsNTL>(src_black + pP + goff);
+            r.f1 = gload<T, N, kZsNTL>(f + (pP - P) + goff);
+            r.f2 = gload<T, N, kZsNTL>(f + (pP - 2 * P) + Hh + goff);
+        } else {
+            if constexpr (ZSRC)
+                r.u = vzero<T, N>();
+            else
+                r.u = gload<T, N, kZsNTL>(src_black + (int64_t)pcl(p) * P + goff);
+            r.f1 = gload<T, N, kZsNTL>(f + (int64_t)pcl(p - 1) * P + goff);
+            r.f2 = gload<T, N, kZsNTL>(f + (int64_t)pcl(p - 2) * P + Hh + goff);
+        }
+    };
+    // W0: A0 black at p-2 .. p; W1: A1 red at p-3 .. p-1; W2: A2 black at p-4 .. p-2; FR: red f of planes
+    // p-3 .. p-1 (plane q in slot (q - zlo) & 3; every step knows its slot offset at compile time, as k_zs)
+    VT W0[4], W1[4], W2[4], FR[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) W0[i] = W1[i] = W2[i] = FR[i] = vz;
+    // ro: the wave's role (0, 1: every stage of the group; 2: rows d >= 4, stage 1 only)
+    auto step_a = [&](auto st, auto rt, const PF& cur, PF& nxt, int p, int ro) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        constexpr int RS = decltype(rt)::value;  // (p - zlo) & 3
+        auto sl = [](int k) constexpr { return (RS - k) & 3; };  // ring slot of plane p - k
+        if (ST) p = (p & ~1) | ((H + RS) & 1);  // steady: Z0 even, so p's parity is zlo's plus RS
+        zs_hold<T, N>(cur.u);
+        zs_hold<T, N>(cur.f1);
+        zs_hold<T, N>(cur.f2);
+        asm volatile("" ::: "memory");
+        if (ST || p + PFD <= p_end) prefetch_a(st, nxt, p + PFD);
+        ZsNb<T, N> n1, n2, n3;
+        VT a0 = cur.u;
+        if (!ST && !inz(p)) a0 = vz;
+        W0[sl(0)] = a0;
+        zs_nb_load<T, N>(n1, slot(0, 2, p - 1), col);
+        VT o1 = zs_relax<T, N, true, ST>(W0[sl(2)], W0[sl(1)], W0[sl(0)], n1, cur.f1, col, par(p - 1), 0, g.nx, op, dz);
+        if (!ST && !inz(p - 1)) o1 = vz;
+        W1[sl(1)] = o1;
+        VT o2 = vz, o3 = vz;
+        if (ro < 2) {
+            zs_nb_load<T, N>(n2, slot(S::OFF1, 2, p - 2), col);
+            o2 = zs_relax<T, N, true, ST>(W1[sl(3)], W1[sl(2)], W1[sl(1)], n2, cur.f2, col, 1 ^ par(p - 2), 0, g.nx, op, dz);
+            if (!ST && !inz(p - 2)) o2 = vz;
+            W2[sl(2)] = o2;
+            zs_nb_load<T, N>(n3, slot(S::OFF2, 2, p - 3), col);
+            o3 = zs_relax<T, N, true, ST>(W2[sl(4)], W2[sl(3)], W2[sl(2)], n3, FR[sl(3)], col, par(p - 3), 0, g.nx, op, dz);
+            if (!ST && !inz(p - 3)) o3 = vz;
+        }
+        if (in_xy) {  // (slots no stage of this step reads; columns outside the box stay 0)
+            vstore<T, N>(slot(0, 2, p) + col.lrow, a0);
+            vstore<T, N>(slot(S::OFF1, 2, p - 1) + col.lrow, o1);
+            if (ro < 2) {
+                vstore<T, N>(slot(S::OFF2, 2, p - 2) + col.lrow, o2);
+                vstore<T, N>(slot(S::OFF3, NS3, p - 3) + col.lrow, o3);
+            }
+            if (frow) {  // B reads them three steps later (stage 4: black f of plane p - 5, the residual: red f of p - 6)
+                vstore<T, N>(fslot(SP::OFFFR, p - 3), FR[sl(3)]);
+                vstore<T, N>(fslot(SP::OFFFB, p - 2), cur.f2);
+            }
+        }
+        FR[sl(1)] = cur.f1;  // red f of plane p - 1
+    };
+
+    // ---- group B: stage 4, the smoothed black plane, the residual + restriction (tile waves only) ----
+    auto prefetch_b = [](auto, PF&, int) {};  // (no global loads: its f comes from A through LDS)
+    // W3: A3 red at p-6 .. p-4 (from LDS); W4: A4 black at p-7 .. p-5; FB: black f of planes p-6, p-5; AS: stage
+    // 4's askew of the last two steps (ZS_RASK); acc: the restriction's sum
+    VT W3[4], W4[4], FB[4];
+    T AS[2][N], acc[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) AS[0][e] = AS[1][e] = acc[e] = (T)0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) W3[i] = W4[i] = FB[i] = vz;
+    const bool even_row = (gy & 1) == 0;
+    T* const xbase = lds + S::OFFX + (((ye + (H & 1)) >> 1) * G + gx) * 2 * N;
+    auto xs = [&](int q) { return xbase + (q & 1) * (S::XPAIRS * G * 2 * N); };
+    // tw: a tile wave (the others run stage 4 only)
+    auto step_b = [&](auto st, auto rt, auto tw, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        constexpr int RS = decltype(rt)::value;  // (p - zlo) & 3
+        auto sl = [](int k) constexpr { return (RS - k) & 3; };  // ring slot of plane p - k
+        if (ST) p = (p & ~1) | ((H + RS) & 1);
+        const int zz0 = ST ? (z0 & ~1) : z0;
+        ZsNb<T, N> n4, nk;
+        const VT fb = vload<T, N>(fslot(SP::OFFFB, p - 5));  // black f of plane p - 5
+        // ---- stage 4 on plane p - 5: A's stage-3 planes p - 6 .. p - 4, the newest written one step ago ----
+        W3[sl(4)] = vload<T, N>(slot(S::OFF3, NS3, p - 4) + col.lrow);
+        zs_nb_load<T, N>(n4, slot(S::OFF3, NS3, p - 5), col);
+        VT o4 = zs_relax_a<T, N, true, ST>(W3[sl(6)], W3[sl(5)], W3[sl(4)], n4, fb, col, 1 ^ par(p - 5), 0, g.nx, op, dz,
+                                           AS[RS & 1]);
+        if (!ST && !inz(p - 5)) o4 = vz;
+        W4[sl(5)] = o4;
+        if (in_xy) vstore<T, N>(slot(S::OFF4, 2, p - 5) + col.lrow, o4);
+        if constexpr (decltype(tw)::value) {
+            // ---- the smoothed plane p - 5: its black cells (POST never reads the red ones, see k_zs) ----
+            {
+                const int q = p - 5;
+                if (q >= Z0 && q < Z0 + zc && tile_xy) gstore<T, N, kZsNTS>(dst + (int64_t)q * P + Hh + goff, o4);
+            }
+            // ---- residual + restriction of plane p - 6 ----
+            const int q = p - 6;
+            const int pq = par(q);
+            zs_nb_load<T, N>(nk, slot(S::OFF4, 2, q), col);  // black of A4 at q
+            T xr[2 * N];
+            {
+                const T* x = xs(q - 1);  // the odd row's residuals of plane q - 1 (even rows read them)
+#pragma unroll
+                for (int e = 0; e < 2 * N; ++e) xr[e] = x[e];
+            }
+            // red cells (x parity pq) see black neighbours; the black cells' neighbours are the red cells of the last
+            // step's stage 4 (its askew, ZS_RASK)
+            T rred[N], rblk[N], rr[2][N];  // rr: [x parity][e]
+            const VT fr = vload<T, N>(fslot(SP::OFFFR, q));  // red f of plane q
+            zs_residual<T, N, true, ST>(W4[sl(7)], W4[sl(6)], W4[sl(5)], nk, W3[sl(6)], fr, col, pq, 0, g.nx, op, dz, rred);
+            zs_residual_a<T, N, true, ST>(AS[(RS & 1) ^ 1], W4[sl(6)], FB[sl(6)], col, 1 ^ pq, 0, g.nx, op, dz, rblk);
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                rr[0][e] = pq == 0 ? rred[e] : rblk[e];
+                rr[1][e] = pq == 0 ? rblk[e] : rred[e];
+            }
+            const int dq = q - (ST ? (Z0 & ~1) : Z0);
+            if (dq >= 0 && dq <= zc && tile_xy)
+                zs_restrict_avg<T, N>(rr, xr, acc, dq, zc, even_row, xs(q), R, (zz0 + q - 1) >> 1, gy >> 1, col.gm, cz0, gc);
+            FB[sl(5)] = fb;  // black f of plane p - 5
+        }
+    };
+
+    if (wk == 0) {
+        const int wrole = S::wave_role(lw);
+        run(prefetch_a, [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+            step_a(st, rt, cur, nxt, p, decltype(st)::value ? wrole : 0);  // (every generic step runs the full work)
+        });
+    } else if (wk == 1) {
+        if (lw < SP::NTW)
+            run(prefetch_b, [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+                step_b(st, rt, STY, p);
+            });
+        else
+            run(prefetch_b, [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+                step_b(st, rt, GEN, p);
+            });
+    } else {
+        // (two separate conditionals, not an if / else: the compiler merges the two arms' stores into one store
+        // through a selected address, which puts the rings in private memory)
+        run(
+            [&](auto st, PF& r, int p) __attribute__((always_inline)) {
+                if (!grp_b) prefetch_a(st, r, p);
+            },
+            [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+                if (!grp_b) step_a(st, rt, cur, nxt, p, 2);
+                asm volatile("" ::: "memory");
+                if (grp_b) step_b(st, rt, GEN, p);
+            });
+    }
 }
 
 // ---- y-streamed temporally blocked smoothing (2D, red/black 2+2) -------------------------------
@@ -4548,6 +4886,7 @@ FusedTuning fused_tuning_from_env()
     t.patch_post = parse_patch(std::getenv("MGP_ZS_PATCH_POST"), vb ? both : -1);
     if (const char* v = std::getenv("MGP_ZS_FWF")) t.fwf = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_ZS_POST_ZC")) t.post_zc = std::max(0, std::atoi(v));
+    if (const char* v = std::getenv("MGP_ZS_SPLIT")) t.split = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_STAMP_R")) t.stamp_r = std::atoi(v) != 0;
     return t;
 }
@@ -4582,6 +4921,24 @@ static hipError_t zs_launch(const FusedArgs& a, hipStream_t s)
                                                                            op, (T)a.clc, a.zc, a.ghost,
                                                                            zs_patch(PRE ? a.tu.patch_pre : a.tu.patch_post,
                                                                                     a.g.nx / S::TX, a.g.ny / S::TY, nb));
+    return hipGetLastError();
+}
+
+// PRE with the 2^3-average restriction, fp32, cl = 0: the stage-split kernel (ZSRC: a fresh zero guess)
+template <bool ZSRC>
+static hipError_t zs_split_launch(const FusedArgs& a, hipStream_t s)
+{
+    using SP = ZsSplit<float>;
+    using S = SP::S;
+    const Op<float, 3> op = make_op<float, 3>(a.h, a.cl);
+    const unsigned nb = (unsigned)((a.g.nx / S::TX) * (a.g.ny / S::TY) * (a.g.nz / a.zc));
+    if (a.info) {  // rocprofv3's spelling of the instantiation
+        std::snprintf(a.info->name, sizeof a.info->name, "k_zs_split<float, %s>", tf(ZSRC));
+        a.info->grid = (int64_t)nb * SP::NTL;
+    }
+    k_zs_split<float, ZSRC><<<nb, SP::NTL, SP::lds_bytes, s>>>((const float*)a.src, (const float*)a.f, (float*)a.dst,
+                                                                (float*)a.R, a.g, a.gc, op, a.zc, a.ghost,
+                                                                zs_patch(a.tu.patch_pre, a.g.nx / S::TX, a.g.ny / S::TY, nb));
     return hipGetLastError();
 }
 
@@ -4644,6 +5001,9 @@ static hipError_t fused_dispatch(const FusedArgs& a, hipStream_t s)
             return a.src ? zs_launch<T, true, 2, false, CLZ>(a, s) : zs_launch<T, true, 2, true, CLZ>(a, s);
     }
     if (a.pre && a.linear == 2) return hipErrorInvalidValue;
+    if constexpr (std::is_same<T, float>::value && CLZ) {
+        if (a.pre && !a.linear && a.tu.split) return a.src ? zs_split_launch<false>(a, s) : zs_split_launch<true>(a, s);
+    }
     if (a.pre && !a.src)  // a fresh zero guess (ERR marks it in PRE)
         return a.linear ? zs_launch<T, true, 1, true, CLZ>(a, s) : zs_launch<T, true, 0, true, CLZ>(a, s);
     if (a.pre) return a.linear ? zs_launch<T, true, 1, false, CLZ>(a, s) : zs_launch<T, true, 0, false, CLZ>(a, s);
@@ -4774,6 +5134,11 @@ static hipError_t fused_attr()
         if (e != hipSuccess) return e;
     }
     hipError_t e = hipFuncSetAttribute((const void*)k_zs<T, true, 0, false, CLZ>, A, pre);
+    if constexpr (std::is_same<T, float>::value && CLZ) {
+        const int w = (int)ZsSplit<float>::lds_bytes;
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, false>, A, w);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, true>, A, w);
+    }
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs<T, true, 1, false, CLZ>, A, pre);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs<T, true, 0, true, CLZ>, A, pre);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs<T, true, 1, true, CLZ>, A, pre);
