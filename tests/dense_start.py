@@ -1,10 +1,10 @@
-"""Dense random level-0 start states for whole-cycle parity (test_gpu_dense.py) and their CPU guard
+"""Dense random level-0 start states for whole-cycle parity (test_gpu_dense.py, test_gpu_dense_fw.py) and their CPU guard
 (test_dense_inputs.py) — TEST INFRASTRUCTURE ONLY.
 
 init_point_charge() leaves one non-zero cell in f and in psi and zeros everywhere else, so a cycle started from it
 cannot tell a level-0 load of the wrong f cell (or of u in the first cycle) from the right one: both read a zero.  dense_start()
 gives a context, an oracle or a slab rank the same generic fields instead: psi0 and f0 uniform in [-1, 1) from two
-seeded generators, cast to the real type.  CASES lists every (box, real, options) the GPU file runs, in one place,
+seeded generators, cast to the real type.  CASES lists every (box, real, options) the GPU files run, in one place,
 so that the CPU guard can hold the reference to the conditions the GPU comparison relies on (finite, no zero and no
 subnormal cell, err falling) for exactly those inputs.
 """
@@ -46,6 +46,8 @@ def dense_start(x, seed):
 
 RB = dict(smoother="rbgs", nu1=2, nu2=2)
 LC = dict(prolong="linear", coarse_bc="consistent")
+FW = dict(restriction="full_weighting")
+RAW = dict(real="float", arith="double")
 
 # id -> (make_opts / Oracle keywords, seed).  The ids name the engine the GPU file drives with the case; the seeds
 # are distinct (seed + 1 seeds f; the reset cases use seed + 10 and seed + 11 for their second pair of fields).
@@ -101,8 +103,50 @@ CASES = {
     # 9. loopback slabs, world 2 (test_split_loopback_slabs' box)
     "slab-zs-64": (dict(dim=3, n=(64, 64, 64), real="float", **RB, **LC), 661),
     "slab-piece-64-f64": (dict(dim=3, n=(64, 64, 64), real="double", **RB, **LC), 681),
+    # ---- test_gpu_dense_fw.py: the two kernel families that have load paths of their own ----
+    # 10. the full weighting (FW).  fused into k_zs PRE (LINEAR 2: fp32, cl = 0): one tile with every face a box
+    # face, 2 x 2 PRE tiles, two fused levels (level 1 restricts a dense residual from a fresh guess), the F-cycle
+    "fw-zs-64x32x16": (dict(dim=3, n=(64, 32, 16), real="float", **RB, **LC, **FW), 701),
+    "fw-zs-128x64x32": (dict(dim=3, n=(128, 64, 32), real="float", **RB, **LC, **FW), 721),
+    "fw-zs-128-pc-zero": (dict(dim=3, n=(128, 128, 128), real="float", prolong="pc", coarse_bc="zero", **RB, **FW), 741),
+    "fw-zs-64-F": (dict(dim=3, n=(64, 64, 64), real="float", cycle="F", **RB, **LC, **FW), 761),
+    # fp64: k_zs PRE LINEAR 1 (smoothing only), then k_resfw with 2 x 4 tiles and z-chunk seams
+    "fw-zs-f64-128x64x32": (dict(dim=3, n=(128, 64, 32), real="double", **RB, **LC, **FW), 781),
+    "fw-zs-f64-128x64x32-zero": (dict(dim=3, n=(128, 64, 32), real="double", prolong="linear", coarse_bc="zero",
+                                      **RB, **FW), 801),
+    # k_resfw on a per-piece level 0 (3D: two x tiles, two y tiles, four z-chunks; 2D: 2 x 2 tiles) against the
+    # two-pass path, and a box with no level k_resfw supports (nx % 64 != 0 on all of them)
+    "fw-resfw-128x32x16-f64": (dict(dim=3, n=(128, 32, 16), real="double", **RB, **LC, **FW), 821),
+    "fw-resfw-128x32x16-f32-jacobi": (dict(dim=3, n=(128, 32, 16), real="float", smoother="jacobi", nu1=2, nu2=2,
+                                           **LC, **FW), 841),
+    "fw-resfw-128x64-f64": (dict(dim=2, n=(128, 64, 1), real="double", **RB, **LC, **FW), 861),
+    "fw-resfw-128x64-f32-zero": (dict(dim=2, n=(128, 64, 1), real="float", prolong="linear", coarse_bc="zero",
+                                      **RB, **FW), 881),
+    "fw-two-32x16x8-f32": (dict(dim=3, n=(32, 16, 8), real="float", **RB, **LC, **FW), 901),
+    # k_blk's PRE, both coarse tails, k_ys + k_resfw
+    "fw-blk-64x16x32-f64": (dict(dim=3, n=(64, 16, 32), real="double", smoother="rbgs", nu1=1, nu2=1, **LC, **FW), 921),
+    "fw-blk-128-f64": (dict(dim=2, n=(128, 128, 1), real="double", smoother="rbgs", nu1=2, nu2=1, **LC, **FW), 941),
+    "fw-tail-64x32x16-f32": (dict(dim=3, n=(64, 32, 16), real="float", smoother="jacobi", nu1=3, nu2=2, cycle="F",
+                                  coarse_init="warm", **LC, **FW), 961),
+    "fw-tailc-32x32x64-f64": (dict(dim=3, n=(32, 32, 64), real="double", cycle="F", coarse_init="warm", **RB, **LC,
+                                   **FW), 981),
+    "fw-ys-1024-f32": (dict(dim=2, n=(1024, 1024, 1), real="float", **RB, **LC, **FW), 1001),
+    "fw-ys-1024x512-f64": (dict(dim=2, n=(1024, 512, 1), real="double", **RB, **LC, **FW), 1021),
+    # loopback slabs, world 2 (the per-piece case sets its second pair of fields, seed + RESET_SEED_OFFSET, after
+    # two cycles)
+    "fw-slab-zs-64": (dict(dim=3, n=(64, 64, 64), real="float", **RB, **LC, **FW), 1041),
+    "fw-slab-piece-64-f64": (dict(dim=3, n=(64, 64, 64), real="double", **RB, **LC, **FW), 1061),
+    # 11. cpu-raw.lua's float arithmetic (float buffers, double expressions): its own kernels on every level
+    "raw-64-jacobi": (dict(dim=2, n=(64, 64, 1), **RAW), 1081),  # the reference configuration
+    "raw-32x16x8-rbgs": (dict(dim=3, n=(32, 16, 8), **RAW, **RB, **LC), 1101),
+    "raw-64x32-gslex": (dict(dim=2, n=(64, 32, 1), smoother="gs_lex", **RAW), 1121),
+    "raw-32-fw": (dict(dim=3, n=(32, 32, 32), **RAW, **RB, **LC, **FW), 1141),
+    "raw-16x32x16-F-warm": (dict(dim=3, n=(16, 32, 16), smoother="jacobi", nu1=3, nu2=2, cycle="F",
+                                 coarse_init="warm", **RAW, **LC), 1161),
 }
-RESET_SEED_OFFSET = 10  # the second pair of fields of the "reset-*" cases: seed + 10 (psi), seed + 11 (f)
+RESET_SEED_OFFSET = 10  # the second pair of fields of the cases in SECOND_FIELDS: seed + 10 (psi), seed + 11 (f)
+# the cases that set level 0 again in mid-run
+SECOND_FIELDS = ("reset-zs-64", "reset-piece-256-f64", "fw-slab-piece-64-f64")
 
 
 def case(cid):

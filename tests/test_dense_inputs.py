@@ -1,4 +1,5 @@
-"""CPU guard of the dense start states (dense_start.py) that test_gpu_dense.py compares the GPU with the oracle on.
+"""CPU guard of the dense start states (dense_start.py) that test_gpu_dense.py and test_gpu_dense_fw.py compare the
+GPU with the oracle on.
 
 The GPU comparison is bit for bit, so it needs inputs on which a mismatch can only be an indexing or ordering
 error: for every (box, real, options) of dense_start.CASES, three oracle steps from the dense start must leave psi
@@ -15,12 +16,13 @@ grows past its first value is not admitted at all: dense_start.py names the one 
 import numpy as np
 import pytest
 
-from dense_start import CASES, RESET_SEED_OFFSET, case, dense_fields, dense_start, oracle_kw
+from dense_start import CASES, RESET_SEED_OFFSET, SECOND_FIELDS, case, dense_fields, dense_start, oracle_kw
 from oracle_lib import Oracle
 
 NOT_MONOTONE = {"ys-1024x512-f64-zero", "blk2-512x256-f32"}
 
-STARTS = [(cid, 0) for cid in CASES] + [(cid, RESET_SEED_OFFSET) for cid in CASES if cid.startswith("reset-")]
+assert all(cid in SECOND_FIELDS for cid in CASES if cid.startswith("reset-"))
+STARTS = [(cid, 0) for cid in CASES] + [(cid, RESET_SEED_OFFSET) for cid in CASES if cid in SECOND_FIELDS]
 
 
 @pytest.mark.parametrize("cid,offset", STARTS, ids=[c if not s else f"{c}-second-fields" for c, s in STARTS])

@@ -32,7 +32,7 @@ SPLIT_NAME = "k_zs_split<float, false>"
 # every switch a case may set; a variant's environment is these cleared, then its own
 SWITCHES = ("MGP_FUSED", "MGP_FUSED_MIN_CELLS", "MGP_ZPOST_MIN_CELLS", "MGP_ZS_SPLIT", "MGP_ZS_WIDE", "MGP_LAZY_ZERO",
             "MGP_YS_MIN_CELLS", "MGP_YS_HALF", "MGP_BLK", "MGP_BLK2", "MGP_BRES", "MGP_TAIL", "MGP_TAIL_CUBIC",
-            "MGP_FRESH", "MGP_GRAPH")
+            "MGP_FRESH", "MGP_GRAPH", "MGP_RESFW", "MGP_ZS_FWF")
 
 
 def _mg():
