@@ -129,8 +129,9 @@ const char* mgp_last_error(const mgp_ctx* c);
 
 /* Level hierarchy.  info[0..7] = {nx, ny, nz_global, nz_local, z0, distributed, engine, exchanges}; engine =
  * how a cycle runs the level's smoothing phases: 0 one launch per piece, 1 inside the single-launch coarse
- * tail (LDS-resident levels), 2 temporally blocked z-streamed phases, 3 3D-tiled one-launch phases, 4 PRE one
- * launch per piece and POST temporally blocked; exchanges =
+ * tail (LDS-resident levels), 2 temporally blocked z-streamed phases, 3 3D-tiled one-launch phases, 4 POST
+ * temporally blocked, PRE one launch per piece or, where supported (fp32, 2^3-average restriction, one rank's whole
+ * level, from a fresh guess; MGP_ZPOST_PRE=0: never), the stage-split temporally blocked PRE; exchanges =
  * halo exchanges (grouped send/recv with the z-neighbours) of this level so far on this rank. */
 int         mgp_num_levels(const mgp_ctx* c);
 int         mgp_level_info(const mgp_ctx* c, int level, int64_t info[8]);
@@ -349,6 +350,8 @@ int         mgp_set_debug(mgp_ctx* c, int mode);
  *                          2.5 with the full weighting, which restricts after the phase)
  *   MGP_TIMING_FUSED_POST  temporally blocked prolongation + correction + nu2 sweeps (+ err): (2.5 + 2^-dim
  *                          [+ 1 psiOld]) reals per cell
+ *   MGP_TIMING_FUSED_PRE_SUB / _POST_SUB  the same two phases on the levels >= 1 that run them temporally blocked,
+ *                          timed, counted and named (mgp_timing_kernel) exactly as the level-0 kinds
  *   MGP_TIMING_EXCHANGE    every halo exchange of any level (grouped send/recv with the z-neighbours, on the
  *                          compute or the side stream); bytes = what this rank sends
  *   MGP_TIMING_COLLECTIVE  the agglomeration all-gather and the err all-reduce; bytes = what this rank sends
@@ -357,10 +360,12 @@ int         mgp_set_debug(mgp_ctx* c, int mode);
  * mgp_timing_read returns, for one kind, the summed milliseconds, the number of timed launches / calls and
  * their bytes (algorithmic for the kernels: SURVEY.md §8d, not measured traffic). */
 enum { MGP_TIMING_HALF_SWEEP = 0, MGP_TIMING_FUSED_PRE = 1, MGP_TIMING_FUSED_POST = 2, MGP_TIMING_EXCHANGE = 3,
-       MGP_TIMING_COLLECTIVE = 4, MGP_TIMING_REFINE_DEFECT = 5, MGP_TIMING_REFINE_ADD = 6, MGP_TIMING_KINDS = 7 };
+       MGP_TIMING_COLLECTIVE = 4, MGP_TIMING_REFINE_DEFECT = 5, MGP_TIMING_REFINE_ADD = 6, MGP_TIMING_FUSED_PRE_SUB = 7,
+       MGP_TIMING_FUSED_POST_SUB = 8, MGP_TIMING_KINDS = 9 };
 int         mgp_timing(mgp_ctx* c, int enable);
 int         mgp_timing_read(mgp_ctx* c, int kind, double* ms_total, int64_t* launches, double* bytes);
-/* The kernel the last timed launch of a kind ran (MGP_TIMING_FUSED_PRE / _POST; level 0): its symbol with the
+/* The kernel the last timed launch of a kind ran (MGP_TIMING_FUSED_PRE / _POST: level 0; _PRE_SUB / _POST_SUB: the
+ * last such launch of a level >= 1): its symbol with the
  * template arguments as rocprofv3 prints it (NUL-terminated, truncated to cap bytes) and its grid in work-items
  * (rocprofv3's Grid_Size), so that PMC counters measured separately can be matched to exactly this launch.
  * MGP_ERR_STATE when no launch of that kind was timed since mgp_timing(c, 1).  No reference counterpart

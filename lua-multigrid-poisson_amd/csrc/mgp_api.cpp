@@ -168,6 +168,7 @@ struct Level {
     bool fused = false;     // smoothing phases run temporally blocked (k_zs); needs t
     bool blk = false;       // smoothing phases run as 3D-tiled one-launch phases (k_blk); needs t
     bool zpost = false;     // PRE one launch per piece, POST temporally blocked (k_zs); needs t
+    bool zpre = false;      // zpost: PRE from a fresh guess as the stage-split fused PRE (k_zs_split_cl, zc_pre)
     bool zero_pending = false;  // u is logically 0: the next red half-sweep reads c->zbuf instead
     bool ghost_zero = false;    // u is 0 everywhere, so ghost planes of any depth are current
     int64_t exchanges = 0;      // halo exchanges of this level so far (mgp_level_info info[7])
@@ -1236,6 +1237,7 @@ int fused_pre(mgp_ctx* c, int l, double h)
     const bool fwf = fw && mgp::fused_fwf_supported(c->rb, c->o.dim, coarse_coef(c->o.coarse_bc, l) == 0.0, L.p.dist, c->tu);
     mgp::FusedArgs a{};
     a.tu = c->tu;
+    if (L.zpre) a.tu.split_cl = true;  // (a zpost level's fused PRE is the split kernel's: MGP_ZPOST_PRE is its switch)
     a.pre = true;
     a.linear = fwf ? 2 : fw;  // PRE: 1 = smoothing only (both colours stored), the full weighting follows
     a.clc = coarse_coef(c->o.coarse_bc, l + 1);  // (the fused full weighting's face weight 3 - c)
@@ -1249,14 +1251,16 @@ int fused_pre(mgp_ctx* c, int l, double h)
     a.cl = coarse_coef(c->o.coarse_bc, l);
     a.zc = L.zc_pre;
     a.ghost = c->G;
-    if (l == 0 && c->timing) a.info = &c->t_info[MGP_TIMING_FUSED_PRE];
+    // (levels >= 1 are timed and named as kinds of their own: level 0's stay the finest level's)
+    const int kind = l == 0 ? MGP_TIMING_FUSED_PRE : MGP_TIMING_FUSED_PRE_SUB;
+    if (c->timing) a.info = &c->t_info[kind];
     hipEvent_t e;
-    TRY(timed_begin(c, l, &e));
+    TRY(l == 0 ? timed_begin(c, l, &e) : timed_begin_on(c, c->s, &e));
     HIP_TRY(c, mgp::launch_fused(c->rb, a, c->s));
     // algorithmic bytes (include/mgpoisson.h): read black u and f, write black u and R / 2^dim
     // (full weighting: both colours of u, the restriction runs after the phase)
     const double coarse = std::ldexp(1.0, -c->o.dim);
-    TRY(timed_end(c, e, MGP_TIMING_FUSED_PRE, (fw && !fwf ? 2.5 : 2.0 + coarse) * c->rb * (double)level_cells(L)));
+    TRY(timed_end(c, e, kind, (fw && !fwf ? 2.5 : 2.0 + coarse) * c->rb * (double)level_cells(L)));
     std::swap(L.u, L.t);  // u = smoothed; t = the previous iterate (psiOld on level 0)
     L.zero_pending = false;
     L.ghost_ok = !L.p.dist;
@@ -1306,12 +1310,13 @@ int fused_post(mgp_ctx* c, int l, double h, bool want_err)
     a.clc = coarse_coef(c->o.coarse_bc, l + 1);
     a.zc = L.zc;
     a.ghost = c->G;
-    if (l == 0 && c->timing) a.info = &c->t_info[MGP_TIMING_FUSED_POST];
+    const int kind = l == 0 ? MGP_TIMING_FUSED_POST : MGP_TIMING_FUSED_POST_SUB;
+    if (c->timing) a.info = &c->t_info[kind];
     hipEvent_t e;
-    TRY(timed_begin(c, l, &e));
+    TRY(l == 0 ? timed_begin(c, l, &e) : timed_begin_on(c, c->s, &e));
     HIP_TRY(c, mgp::launch_fused(c->rb, a, c->s));
     // read black u, V / 2^dim, f (and psiOld with err), write u
-    TRY(timed_end(c, e, MGP_TIMING_FUSED_POST,
+    TRY(timed_end(c, e, kind,
                   (2.5 + std::ldexp(1.0, -c->o.dim) + (want_err ? 1.0 : 0.0)) * c->rb * (double)level_cells(L)));
     if (keep)
         std::swap(L.u, c->xbuf);  // u = new iterate, t = psiOld (kept), xbuf = the smoothed PRE output (scratch)
@@ -1672,7 +1677,11 @@ int cycle_rec(mgp_ctx* c, int l, double h, bool fcycle, bool pre_done = false, b
     const bool zpost = c->lev[l].zpost && h == level_h(c, l);
     std::optional<Range> pre_range(std::in_place, "L%d pre-smooth + restrict", l);
     const bool pre2 = !pre_done && blk && pre2_ok(c, l, h, fcycle);
+    // a zpost level's PRE from a fresh guess: one stage-split launch (a warm guess keeps the pieces: see select_engines)
+    const bool zpre = zpost && c->lev[l].zpre && c->lev[l].zero_pending;
     if (pre_done) {
+    } else if (zpre) {
+        TRY(fused_pre(c, l, h));
     } else if (fused) {
         TRY(fused_pre(c, l, h));
         TRY(early_exchange_post(c, l));
@@ -2189,7 +2198,7 @@ static void select_engines(mgp_ctx* c)
         c->err_fuse = false;
         c->fresh_sweep = false;
         c->post1 = false;
-        for (auto& L : c->lev) L.fused = L.blk = L.zpost = false;
+        for (auto& L : c->lev) L.fused = L.blk = L.zpost = L.zpre = false;
         c->tail_level = -1;
         return;
     }
@@ -2222,7 +2231,15 @@ static void select_engines(mgp_ctx* c)
         for (size_t l = 1; l + 1 < c->lev.size(); ++l) {
             Level& L = c->lev[l];
             L.zpost = on && !L.fused && level_cells(L) >= zmin && mgp::fused_supported(c->rb, c->o.dim, 2, L.g, c->tu);
-            if (L.zpost) L.zc = mgp::fused_zc(c->rb, L.g, false, coarse_coef(c->o.coarse_bc, (int)l) == 0.0, c->tu);
+            const bool clz = coarse_coef(c->o.coarse_bc, (int)l) == 0.0;
+            if (L.zpost) L.zc = mgp::fused_zc(c->rb, L.g, false, clz, c->tu);
+            // Its PRE as the stage-split fused PRE where that kernel applies: fp32, a boundary-modified operator, the
+            // 2^3-average restriction, one rank's whole level (a slab's comm plan would change), and only from a
+            // fresh guess (decided per visit in cycle_rec: a warm guess would take k_zs, which lost to the pieces
+            // here).  MGP_ZPOST_PRE=0 / MGP_ZS_SPLIT=0 keep the pieces.
+            L.zpre = L.zpost && !L.p.dist && c->rb == 4 && !clz && c->o.restriction == MGP_RESTRICT_AVERAGE &&
+                     c->tu.zpost_pre && c->tu.split;
+            if (L.zpre) L.zc_pre = mgp::fused_zc(c->rb, L.g, true, clz, c->tu);
             if (L.zpost && L.p.dist) c->G = mgp::kGhostZs;
         }
     }

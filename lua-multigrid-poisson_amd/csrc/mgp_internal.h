@@ -172,6 +172,12 @@ struct FusedTuning {
     bool fwf = true;     // MGP_ZS_FWF=0: the full weighting after the fused PRE instead of inside it
     int post_zc = 256;   // MGP_ZS_POST_ZC: POST's z-chunks hold at most this many planes (0: no limit)
     bool split = true;   // MGP_ZS_SPLIT=0: fp32 cl = 0 PRE (2^3 average) on k_zs instead of the stage-split k_zs_split
+    // MGP_ZS_SPLIT_CL=1: a fused cl != 0 level's fp32 PRE from a fresh guess on k_zs_split_cl instead of k_zs (off:
+    // on the slab workloads its gain, 1.4-1.9 % per interleaved pair, stayed inside the round-to-round drift)
+    bool split_cl = false;
+    // MGP_ZPOST_PRE=0: the PRE of a `zpost` level one launch per piece, also where k_zs_split_cl applies (on: the
+    // 256^3 level of the 512^3 box, 87 -> 57 us)
+    bool zpost_pre = true;
     bool stamp_r = false;  // MGP_STAMP_R=1 (ZS_STAMP timing builds only): POST's wall-clock stamps go to level l+1's f
 };
 FusedTuning fused_tuning_from_env();

@@ -1724,13 +1724,25 @@ __device__ __forceinline__ void zs_dvals(const ZsDiag<T>& dz, T& db, T& yb, T& d
     asm("" : "+v"(db), "+v"(yb), "+v"(de), "+v"(ye));
 }
 
+// The diagonals of a step's cells: the steady ones (dz), or, in a generic step (TAB), the row's table entries for
+// its nbyz y / z faces (Op::row_diag: the table Markstein form of Op::relax, no IEEE division and no divergent
+// boundary path; dz.left / dz.right mark the x-face cell as in the steady steps)
+template <typename T, bool ST>
+__device__ __forceinline__ void zs_diag(const Op<T, 3>& op, const ZsDiag<T>& dz, int nbyz, T& db, T& yb, T& de, T& ye)
+{
+    if (ST)
+        zs_dvals(dz, db, yb, de, ye);
+    else
+        row_diag_fast(op, nbyz, db, yb, de, ye);
+}
+
 // One half-sweep of my N cells of one colour (x parity o) from the other colour's window
 // (zl, cen, zr) and its in-plane operands: k_half's expressions.  Waves whose cells all have the
 // interior diagonal (every wave of a level with cl = 0) take the reciprocal form, which is what
 // Op::relax computes there.
 // ask: the cells' neighbour sums times 1/h^2 (the askew of k_resrestrict's expression, same operands and
 // order): a PRE black cell's residual one step later sees exactly these neighbours (zs_residual_a)
-template <typename T, int N, bool CLZ, bool ST = false>
+template <typename T, int N, bool CLZ, bool ST = false, bool TAB = false>
 __device__ __forceinline__ Vec<T, N> zs_relax_a(const Vec<T, N>& zl, const Vec<T, N>& cen, const Vec<T, N>& zr,
                                                 const ZsNb<T, N>& nb, const Vec<T, N>& fv, const ZsCol& c, int o,
                                                 int nbyz, int nx, const Op<T, 3>& op, const ZsDiag<T>& dz,
@@ -1741,9 +1753,9 @@ __device__ __forceinline__ Vec<T, N> zs_relax_a(const Vec<T, N>& zl, const Vec<T
     zs_nbsum<T, N>(zl, cen, zr, nb, o, t);
 #pragma unroll
     for (int e = 0; e < N; ++e) ask[e] = t[e] * op.inv_hSq;
-    if (!CLZ && ST) {
+    if (!CLZ && (ST || TAB)) {
         T db, yb, de, ye;
-        zs_dvals(dz, db, yb, de, ye);
+        zs_diag<T, ST>(op, dz, nbyz, db, yb, de, ye);
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const bool edge = (e == 0 && o == 0 && dz.left) || (e == N - 1 && o == 1 && dz.right);
@@ -1762,17 +1774,17 @@ __device__ __forceinline__ Vec<T, N> zs_relax_a(const Vec<T, N>& zl, const Vec<T
     return out;
 }
 
-template <typename T, int N, bool CLZ, bool ST = false>
+template <typename T, int N, bool CLZ, bool ST = false, bool TAB = false>
 __device__ __forceinline__ Vec<T, N> zs_relax(const Vec<T, N>& zl, const Vec<T, N>& cen, const Vec<T, N>& zr,
                                               const ZsNb<T, N>& nb, const Vec<T, N>& fv, const ZsCol& c, int o,
                                               int nbyz, int nx, const Op<T, 3>& op, const ZsDiag<T>& dz)
 {
     T ask[N];
-    return zs_relax_a<T, N, CLZ, ST>(zl, cen, zr, nb, fv, c, o, nbyz, nx, op, dz, ask);
+    return zs_relax_a<T, N, CLZ, ST, TAB>(zl, cen, zr, nb, fv, c, o, nbyz, nx, op, dz, ask);
 }
 
 // Residual of my N cells of one colour (x parity o) at one plane: k_resrestrict's expressions.
-template <typename T, int N, bool CLZ, bool ST = false>
+template <typename T, int N, bool CLZ, bool ST = false, bool TAB = false>
 __device__ __forceinline__ void zs_residual(const Vec<T, N>& zl, const Vec<T, N>& cen, const Vec<T, N>& zr,
                                             const ZsNb<T, N>& nb, const Vec<T, N>& uc, const Vec<T, N>& fv,
                                             const ZsCol& c, int o, int nbyz, int nx, const Op<T, 3>& op,
@@ -1780,9 +1792,9 @@ __device__ __forceinline__ void zs_residual(const Vec<T, N>& zl, const Vec<T, N>
 {
     T t[N];
     zs_nbsum<T, N>(zl, cen, zr, nb, o, t);
-    if (!CLZ && ST) {
+    if (!CLZ && (ST || TAB)) {
         T db, yb, de, ye;
-        zs_dvals(dz, db, yb, de, ye);
+        zs_diag<T, ST>(op, dz, nbyz, db, yb, de, ye);
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const bool edge = (e == 0 && o == 0 && dz.left) || (e == N - 1 && o == 1 && dz.right);
@@ -1807,14 +1819,14 @@ __device__ __forceinline__ void zs_residual(const Vec<T, N>& zl, const Vec<T, N>
 }
 
 // The same residual from the cells' askew (zs_relax_a of the half-sweep that last saw these neighbours)
-template <typename T, int N, bool CLZ, bool ST = false>
+template <typename T, int N, bool CLZ, bool ST = false, bool TAB = false>
 __device__ __forceinline__ void zs_residual_a(const T (&ask)[N], const Vec<T, N>& uc, const Vec<T, N>& fv,
                                               const ZsCol& c, int o, int nbyz, int nx, const Op<T, 3>& op,
                                               const ZsDiag<T>& dz, T (&rr)[N])
 {
-    if (!CLZ && ST) {
+    if (!CLZ && (ST || TAB)) {
         T db, yb, de, ye;
-        zs_dvals(dz, db, yb, de, ye);
+        zs_diag<T, ST>(op, dz, nbyz, db, yb, de, ye);
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const bool edge = (e == 0 && o == 0 && dz.left) || (e == N - 1 && o == 1 && dz.right);
@@ -2689,12 +2701,22 @@ struct ZsSplit {
     static_assert(lds_bytes <= 160 * 1024, "LDS");
 };
 
-template <typename T, bool ZSRC>
-__global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restrict__ src, const T* __restrict__ f,
-                                                                 T* __restrict__ dst, T* __restrict__ R, Geo g, Geo gc,
-                                                                 Op<T, 3> op, int zc, int gz, int patch)
+//
+// CLZ = false (k_zs_split_cl): a level with a boundary-modified operator (cl != 0, the fused levels below the finest and
+// the 256^3 level of the 512^3 box), from a fresh zero guess.  The tile and the layout are the same; the steady steps
+// take k_zs's steady diagonals (ZsDiag, zs_dvals), the generic ones the row's table entries (zs_diag): the table
+// Markstein division equals the plain one for every such divisor (mgp_device.h), so these are bit-identical to k_zs's
+// relax_direct / residual_direct without their divergent IEEE division.  A warm guess (ZSRC = false) stays on k_zs:
+// that instantiation needs 22 VGPRs beyond the 168 of 12 waves and spills.
+template <typename T, bool ZSRC, bool CLZ>
+__device__ __forceinline__ void zs_split_body(const T* __restrict__ src, const T* __restrict__ f, T* __restrict__ dst,
+                                              T* __restrict__ R, const Geo& g, const Geo& gc, const Op<T, 3>& op, int zc,
+                                              int gz, int patch)
 {
     using SP = ZsSplit<T>;
+    static_assert(CLZ || (ZsShape<T, true, false>::TX == SP::S::TX && ZsShape<T, true, false>::TY == SP::S::TY &&
+                          ZsShape<T, true, false>::N == SP::S::N),
+                  "the split's cl != 0 levels run the cl = 0 tile");
     using S = typename SP::S;
     constexpr int N = S::N, H = S::H, HWE = S::HWE, G = S::G, YE = S::YE, SLOT = S::SLOT, TX = S::TX, TY = S::TY,
                   NS3 = S::NS3;
@@ -2738,7 +2760,7 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
     col.lxm = col.x_first ? col.lrow : col.lrow - N;
     col.lxp = col.x_last ? col.lrow : col.lrow + N;
     const bool in_xy = on && gy >= 0 && gy < g.ny && col.gm >= 0 && col.gm < hw;
-    col.xin = true;  // (cl = 0: unused)
+    col.xin = true;  // (unused: no stage takes k_zs's direct boundary path)
     // columns outside the box load from a clamped in-plane position; their results never reach LDS or HBM
     const int cgy = gy < 0 ? 0 : (gy >= g.ny ? g.ny - 1 : gy);
     const int cgm = col.gm < 0 ? 0 : (col.gm > hw - N ? hw - N : col.gm);
@@ -2749,7 +2771,20 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
     const int lf = frow ? (ye - (H - 1)) * HWE + m0 : 0;
     auto fslot = [&](int off, int q) { return lds + off + (q & 3) * SP::FSLOT + lf; };
     const int zlo = Z0 - H;
-    const ZsDiag<T> dz = {};  // (cl = 0: unused)
+    ZsDiag<T> dz = {};  // (cl = 0: unused)
+    if constexpr (!CLZ) {  // as k_zs
+        const int nby = (gy == 0) + (gy == g.ny - 1);  // 0 .. 2 (ny >= 2)
+        dz.db = nby == 0 ? op.dg[0] : (nby == 1 ? op.dg[1] : op.dg[2]);
+        dz.yb = nby == 0 ? op.ydg[0] : (nby == 1 ? op.ydg[1] : op.ydg[2]);
+        dz.de = nby == 0 ? op.dg[1] : (nby == 1 ? op.dg[2] : op.dg[3]);
+        dz.ye = nby == 0 ? op.ydg[1] : (nby == 1 ? op.ydg[2] : op.ydg[3]);
+        dz.left = col.gm == 0;
+        dz.right = col.gm + N == hw;
+    }
+    // y / z faces of my row at plane q (the generic steps' table index; the steady steps' planes are off the z faces)
+    auto nbyz = [&](int q) {
+        return CLZ ? 0 : (gy == 0) + (gy == g.ny - 1) + (z0 + q == 0) + (z0 + q == gnz - 1);
+    };
     const int p_end = Z0 + zc + 6;
     auto inz = [&](int q) { return z0 + q >= 0 && z0 + q < gnz; };  // inside the global box
     auto pcl = [&](int q) { return q < qlo ? qlo : (q > qhi ? qhi : q); };
@@ -2761,15 +2796,21 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
     for (int i = tid; i < (int)(SP::lds_bytes / sizeof(T)); i += SP::NTL) lds[i] = (T)0;
     __syncthreads();
 
-    // steady steps [ps, pe], as k_zs: every plane a step touches (p .. p - 6) inside the box, the prefetched planes
-    // readable, whole groups of UNR steps, even z0 and Z0 (static plane parity)
+    // steady steps [ps, pe], as k_zs: every plane a step touches (p .. p - 6) inside the box (cl != 0: and every stage's
+    // plane off the z faces), the prefetched planes readable, even z0 and Z0 (static plane parity).  The generic steps
+    // before them are whole groups of UNR steps.  PART (the cl != 0 levels, whose chunks are short): the steady range
+    // ends where it ends, in a partial group that the epilogue completes, so a chunk away from the z faces runs no
+    // generic step at all (rounded to whole groups, 8 of a 32-plane chunk's 44 steps were generic).  Level 0 keeps
+    // whole groups: with every steady step behind a bound test its 268-step launch measured 292 against 276 us, for
+    // 4 generic steps saved.
+    constexpr bool PART = !CLZ;
     int ps = zlo, pe = p_end;
     ps = ps > 7 - z0 ? ps : 7 - z0;
     ps = ps > qlo + 4 ? ps : qlo + 4;
     pe = pe < gnz - 1 - z0 ? pe : gnz - 1 - z0;
     pe = pe < qhi - PFD ? pe : qhi - PFD;
     ps += (UNR - (ps - zlo) % UNR) % UNR;
-    pe -= (pe - ps + 1) % UNR;
+    if (!PART) pe -= (pe - ps + 1) % UNR;
     if (pe < ps || ((z0 | Z0) & 1)) ps = pe = zlo - 1;
     const std::false_type GEN;
     const std::true_type STY;
@@ -2780,18 +2821,27 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
 #pragma unroll
         for (int k = 0; k < PFD; ++k) prefetch(GEN, pb[k], zlo + k);
         int p = zlo;
-        auto group = [&](auto st, int p0, int plim) __attribute__((always_inline)) {
+        // the steps pfirst .. plim of the group of UNR steps from p0 (p0 - zlo a multiple of UNR: ring slot k & 3,
+        // buffers k % NPF and (k + PFD) % NPF)
+        auto group = [&](auto st, int p0, int pfirst, int plim) __attribute__((always_inline)) {
             zs_unroll<UNR>([&](auto kk) __attribute__((always_inline)) {
                 constexpr int k = decltype(kk)::value;
-                if (k == 0 || p0 + k <= plim) {
+                if (p0 + k >= pfirst && p0 + k <= plim) {
                     step(st, std::integral_constant<int, (k & 3)>(), pb[k % NPF], pb[(k + PFD) % NPF], p0 + k);
                     lds_barrier();
                 }
             });
         };
-        for (; p < ps; p += UNR) group(GEN, p, p + UNR);
-        for (; p <= pe; p += UNR) group(STY, p, p + UNR);
-        for (; p <= p_end; p += UNR) group(GEN, p, p_end);
+        for (; p < ps; p += UNR) group(GEN, p, p, p + UNR);
+        for (; p + UNR - 1 <= pe; p += UNR) group(STY, p, p, p + UNR);  // (whole groups: the bound tests fold away)
+        int pf = p;
+        if constexpr (PART) {
+            if (p <= pe) {  // the partial steady group; the epilogue's first group completes it
+                group(STY, p, p, pe);
+                pf = pe + 1;
+            }
+        }
+        for (; p <= p_end; p += UNR) group(GEN, p, PART ? pf : p, p_end);
     };
 
     // ---- group A: stages 0 .. 3 (k_zs's, with its wave roles: rows d >= 4 run stage 1 only) ----
@@ -2836,17 +2886,17 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
         if (!ST && !inz(p)) a0 = vz;
         W0[sl(0)] = a0;
         zs_nb_load<T, N>(n1, slot(0, 2, p - 1), col);
-        VT o1 = zs_relax<T, N, true, ST>(W0[sl(2)], W0[sl(1)], W0[sl(0)], n1, cur.f1, col, par(p - 1), 0, g.nx, op, dz);
+        VT o1 = zs_relax<T, N, CLZ, ST, !CLZ>(W0[sl(2)], W0[sl(1)], W0[sl(0)], n1, cur.f1, col, par(p - 1), nbyz(p - 1), g.nx, op, dz);
         if (!ST && !inz(p - 1)) o1 = vz;
         W1[sl(1)] = o1;
         VT o2 = vz, o3 = vz;
         if (ro < 2) {
             zs_nb_load<T, N>(n2, slot(S::OFF1, 2, p - 2), col);
-            o2 = zs_relax<T, N, true, ST>(W1[sl(3)], W1[sl(2)], W1[sl(1)], n2, cur.f2, col, 1 ^ par(p - 2), 0, g.nx, op, dz);
+            o2 = zs_relax<T, N, CLZ, ST, !CLZ>(W1[sl(3)], W1[sl(2)], W1[sl(1)], n2, cur.f2, col, 1 ^ par(p - 2), nbyz(p - 2), g.nx, op, dz);
             if (!ST && !inz(p - 2)) o2 = vz;
             W2[sl(2)] = o2;
             zs_nb_load<T, N>(n3, slot(S::OFF2, 2, p - 3), col);
-            o3 = zs_relax<T, N, true, ST>(W2[sl(4)], W2[sl(3)], W2[sl(2)], n3, FR[sl(3)], col, par(p - 3), 0, g.nx, op, dz);
+            o3 = zs_relax<T, N, CLZ, ST, !CLZ>(W2[sl(4)], W2[sl(3)], W2[sl(2)], n3, FR[sl(3)], col, par(p - 3), nbyz(p - 3), g.nx, op, dz);
             if (!ST && !inz(p - 3)) o3 = vz;
         }
         if (in_xy) {  // (slots no stage of this step reads; columns outside the box stay 0)
@@ -2889,7 +2939,7 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
         // ---- stage 4 on plane p - 5: A's stage-3 planes p - 6 .. p - 4, the newest written one step ago ----
         W3[sl(4)] = vload<T, N>(slot(S::OFF3, NS3, p - 4) + col.lrow);
         zs_nb_load<T, N>(n4, slot(S::OFF3, NS3, p - 5), col);
-        VT o4 = zs_relax_a<T, N, true, ST>(W3[sl(6)], W3[sl(5)], W3[sl(4)], n4, fb, col, 1 ^ par(p - 5), 0, g.nx, op, dz,
+        VT o4 = zs_relax_a<T, N, CLZ, ST, !CLZ>(W3[sl(6)], W3[sl(5)], W3[sl(4)], n4, fb, col, 1 ^ par(p - 5), nbyz(p - 5), g.nx, op, dz,
                                            AS[RS & 1]);
         if (!ST && !inz(p - 5)) o4 = vz;
         W4[sl(5)] = o4;
@@ -2914,8 +2964,8 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
             // step's stage 4 (its askew, ZS_RASK)
             T rred[N], rblk[N], rr[2][N];  // rr: [x parity][e]
             const VT fr = vload<T, N>(fslot(SP::OFFFR, q));  // red f of plane q
-            zs_residual<T, N, true, ST>(W4[sl(7)], W4[sl(6)], W4[sl(5)], nk, W3[sl(6)], fr, col, pq, 0, g.nx, op, dz, rred);
-            zs_residual_a<T, N, true, ST>(AS[(RS & 1) ^ 1], W4[sl(6)], FB[sl(6)], col, 1 ^ pq, 0, g.nx, op, dz, rblk);
+            zs_residual<T, N, CLZ, ST, !CLZ>(W4[sl(7)], W4[sl(6)], W4[sl(5)], nk, W3[sl(6)], fr, col, pq, nbyz(q), g.nx, op, dz, rred);
+            zs_residual_a<T, N, CLZ, ST, !CLZ>(AS[(RS & 1) ^ 1], W4[sl(6)], FB[sl(6)], col, 1 ^ pq, nbyz(q), g.nx, op, dz, rblk);
 #pragma unroll
             for (int e = 0; e < N; ++e) {
                 rr[0][e] = pq == 0 ? rred[e] : rblk[e];
@@ -2955,6 +3005,23 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restr
                 if (grp_b) step_b(st, rt, GEN, p);
             });
     }
+}
+
+template <typename T, bool ZSRC>
+__global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split(const T* __restrict__ src, const T* __restrict__ f,
+                                                                 T* __restrict__ dst, T* __restrict__ R, Geo g, Geo gc,
+                                                                 Op<T, 3> op, int zc, int gz, int patch)
+{
+    zs_split_body<T, ZSRC, true>(src, f, dst, R, g, gc, op, zc, gz, patch);
+}
+
+// a level with a boundary-modified operator (cl != 0), from a fresh zero guess
+template <typename T>
+__global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split_cl(const T* __restrict__ f, T* __restrict__ dst,
+                                                                    T* __restrict__ R, Geo g, Geo gc, Op<T, 3> op, int zc,
+                                                                    int gz, int patch)
+{
+    zs_split_body<T, true, false>(nullptr, f, dst, R, g, gc, op, zc, gz, patch);
 }
 
 // ---- y-streamed temporally blocked smoothing (2D, red/black 2+2) -------------------------------
@@ -4887,6 +4954,8 @@ FusedTuning fused_tuning_from_env()
     if (const char* v = std::getenv("MGP_ZS_FWF")) t.fwf = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_ZS_POST_ZC")) t.post_zc = std::max(0, std::atoi(v));
     if (const char* v = std::getenv("MGP_ZS_SPLIT")) t.split = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MGP_ZS_SPLIT_CL")) t.split_cl = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MGP_ZPOST_PRE")) t.zpost_pre = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_STAMP_R")) t.stamp_r = std::atoi(v) != 0;
     return t;
 }
@@ -4939,6 +5008,23 @@ static hipError_t zs_split_launch(const FusedArgs& a, hipStream_t s)
     k_zs_split<float, ZSRC><<<nb, SP::NTL, SP::lds_bytes, s>>>((const float*)a.src, (const float*)a.f, (float*)a.dst,
                                                                 (float*)a.R, a.g, a.gc, op, a.zc, a.ghost,
                                                                 zs_patch(a.tu.patch_pre, a.g.nx / S::TX, a.g.ny / S::TY, nb));
+    return hipGetLastError();
+}
+
+// The same on a level with a boundary-modified operator (cl != 0), from a fresh zero guess
+static hipError_t zs_split_cl_launch(const FusedArgs& a, hipStream_t s)
+{
+    using SP = ZsSplit<float>;
+    using S = SP::S;
+    const Op<float, 3> op = make_op<float, 3>(a.h, a.cl);
+    const unsigned nb = (unsigned)((a.g.nx / S::TX) * (a.g.ny / S::TY) * (a.g.nz / a.zc));
+    if (a.info) {
+        std::snprintf(a.info->name, sizeof a.info->name, "k_zs_split_cl<float>");
+        a.info->grid = (int64_t)nb * SP::NTL;
+    }
+    k_zs_split_cl<float><<<nb, SP::NTL, SP::lds_bytes, s>>>((const float*)a.f, (float*)a.dst, (float*)a.R, a.g, a.gc, op, a.zc,
+                                                           a.ghost,
+                                                           zs_patch(a.tu.patch_pre, a.g.nx / S::TX, a.g.ny / S::TY, nb));
     return hipGetLastError();
 }
 
@@ -5003,6 +5089,9 @@ static hipError_t fused_dispatch(const FusedArgs& a, hipStream_t s)
     if (a.pre && a.linear == 2) return hipErrorInvalidValue;
     if constexpr (std::is_same<T, float>::value && CLZ) {
         if (a.pre && !a.linear && a.tu.split) return a.src ? zs_split_launch<false>(a, s) : zs_split_launch<true>(a, s);
+    }
+    if constexpr (std::is_same<T, float>::value && !CLZ) {  // (a warm guess stays on k_zs: that variant would spill)
+        if (a.pre && !a.linear && !a.src && a.tu.split && a.tu.split_cl) return zs_split_cl_launch(a, s);
     }
     if (a.pre && !a.src)  // a fresh zero guess (ERR marks it in PRE)
         return a.linear ? zs_launch<T, true, 1, true, CLZ>(a, s) : zs_launch<T, true, 0, true, CLZ>(a, s);
@@ -5138,6 +5227,10 @@ static hipError_t fused_attr()
         const int w = (int)ZsSplit<float>::lds_bytes;
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, false>, A, w);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, true>, A, w);
+    }
+    if constexpr (std::is_same<T, float>::value && !CLZ) {
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)k_zs_split_cl<float>, A, (int)ZsSplit<float>::lds_bytes);
     }
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs<T, true, 1, false, CLZ>, A, pre);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs<T, true, 0, true, CLZ>, A, pre);

@@ -52,9 +52,11 @@ COARSE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_double, cty
                              ctypes.c_int64)
 TIMING_HALF_SWEEP, TIMING_FUSED_PRE, TIMING_FUSED_POST, TIMING_EXCHANGE, TIMING_COLLECTIVE = 0, 1, 2, 3, 4
 TIMING_REFINE_DEFECT, TIMING_REFINE_ADD = 5, 6
+TIMING_FUSED_PRE_SUB, TIMING_FUSED_POST_SUB = 7, 8  # the temporally blocked launches of levels >= 1
 TIMING_KINDS = {TIMING_HALF_SWEEP: "half_sweep", TIMING_FUSED_PRE: "fused_pre", TIMING_FUSED_POST: "fused_post",
                 TIMING_EXCHANGE: "exchange", TIMING_COLLECTIVE: "collective", TIMING_REFINE_DEFECT: "refine_defect",
-                TIMING_REFINE_ADD: "refine_add"}
+                TIMING_REFINE_ADD: "refine_add", TIMING_FUSED_PRE_SUB: "fused_pre_sub",
+                TIMING_FUSED_POST_SUB: "fused_post_sub"}
 # the fp64 fields of mixed-precision refinement (mgp_refine_set / mgp_refine_get)
 REFINE_PSI, REFINE_F = 0, 1
 COMM_OPS = {0: "exchange", 1: "allgather", 2: "allreduce"}
@@ -211,7 +213,7 @@ def comm_unique_id() -> bytes:
 
 def plan(opts: MGPOpts, max_levels: int = 48):
     """Host-only level plan: list of dicts (nx, ny, nz_global, nz_local, z0, distributed, engine), engine =
-    how mgp_create would run the level's phases ("piece", "tail", "zs", "blk", "zpost": PRE per piece, POST k_zs)."""
+    how mgp_create would run the level's phases ("piece", "tail", "zs", "blk", "zpost": POST k_zs, PRE per piece or the stage-split fused PRE)."""
     rows = (ctypes.c_int64 * (8 * max_levels))()
     n = check(lib.mgp_plan(ctypes.byref(opts), rows, max_levels))
     keys = ("nx", "ny", "nz_global", "nz_local", "z0", "distributed")

@@ -342,7 +342,8 @@ class Context:
 
     def timing_kernels(self):
         """{kind name: (kernel symbol as rocprofv3 prints it, grid in work-items)} of the last timed level-0 fused
-        launch of each kind (mgp_timing_kernel); kinds without a timed launch are absent."""
+        launch of each kind, and of the last one of a level >= 1 ("fused_pre_sub", "fused_post_sub")
+        (mgp_timing_kernel); kinds without a timed launch are absent."""
         out = {}
         for kind, name in L.TIMING_KINDS.items():
             buf, grid = ctypes.create_string_buffer(128), ctypes.c_int64()
