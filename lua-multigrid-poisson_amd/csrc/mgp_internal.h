@@ -178,6 +178,10 @@ struct FusedTuning {
     // MGP_ZPOST_PRE=0: the PRE of a `zpost` level one launch per piece, also where k_zs_split_cl applies (on: the
     // 256^3 level of the 512^3 box, 87 -> 57 us)
     bool zpost_pre = true;
+    // MGP_ZS_SPLIT_POST=0: fp32 cl = 0 POST (trilinear P, the wide tile) on k_zs instead of the stage-split
+    // k_zs_split_post; MGP_ZS_SPLIT_POST_MIN_CELLS: the smallest level (cells per rank) that takes it
+    bool split_post = true;
+    int64_t split_post_min_cells = (int64_t)1 << 27;
     bool stamp_r = false;  // MGP_STAMP_R=1 (ZS_STAMP timing builds only): POST's wall-clock stamps go to level l+1's f
 };
 FusedTuning fused_tuning_from_env();

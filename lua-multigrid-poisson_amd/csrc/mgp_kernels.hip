@@ -1508,10 +1508,12 @@ constexpr bool kZsPreRed = ZS_PRE_RED_STORE != 0;
 
 // FWF (PRE only): the full-weighting restriction fused into the phase (k_zs LINEAR = 2): the residual is needed one
 // cell beyond the tile (the full weighting's 4-cell stencil), so the trapezoid is one stage deeper (H = 6)
-template <typename T, bool PRE, bool CLZ = true, bool WIDE = false, bool FWF = false>
+// NF != 0: that column width instead of the tile's (k_zs_split_post: 16-byte columns on POST's wide tile)
+template <typename T, bool PRE, bool CLZ = true, bool WIDE = false, bool FWF = false, int NF = 0>
 struct ZsShape {
-    static constexpr int N = PRE ? (CLZ ? ZsTile<T>::NPRE : ZsTile<T>::NPRE_CL)
-                                 : (WIDE ? ZsTile<T>::NPOST_W : ZsTile<T>::NPOST);
+    static constexpr int N = NF ? NF
+                                : (PRE ? (CLZ ? ZsTile<T>::NPRE : ZsTile<T>::NPRE_CL)
+                                       : (WIDE ? ZsTile<T>::NPOST_W : ZsTile<T>::NPOST));
     static constexpr int TX = PRE ? (CLZ ? ZsTile<T>::TXPRE : ZsTile<T>::TXPRE_CL)
                                   : (WIDE ? ZsTile<T>::TXPOST_W : ZsTile<T>::TXPOST);
     static constexpr int TY = PRE ? (CLZ ? ZsTile<T>::TYPRE : ZsTile<T>::TYPRE_CL)
@@ -3022,6 +3024,473 @@ __global__ __launch_bounds__((ZsSplit<T>::NTL)) void k_zs_split_cl(const T* __re
                                                                     int gz, int patch)
 {
     zs_split_body<T, true, false>(nullptr, f, dst, R, g, gc, op, zc, gz, patch);
+}
+
+// ---- k_zs POST with its stages split over two groups of waves (fp32, cl = 0, trilinear P, the wide tile) ----
+//
+// The stage split of k_zs_split applied to POST, on 16-byte columns (N = 4 on the 128 x 16 tile: half k_zs's
+// instructions per cell, which at k_zs's one group of 7 waves only made up for the waves it lost):
+//   group A  stage 0 (the prefetched black u + the coarse correction, k_zs's BQ cache) and half-sweeps 1 and 2: at step
+//            p planes p .. p - 2, over the whole extended tile (G x YE threads)
+//   group B  half-sweeps 3 and 4, the err and the stores of the smoothed plane, one step behind: at step p planes
+//            p - 4 and p - 5, over the rows within 1 of the tile
+// The hand-off is stage 2's output, which k_zs leaves in an LDS ring for stage 3's in-plane neighbours: the ring has 4
+// slots here (the fourth is the one A fills meanwhile), and B reads the three planes of its own column from it as well,
+// the newest (plane p - 3) written one step earlier: a register ring for them made B spill.  Stage 4 reads no stage-2
+// value of its own cell, so no other u crosses.  A leaves the f of B's planes in two 4-slot LDS rings over B's rows (red
+// f of plane p - 1, black f of plane p - 2), so B loads no f; B loads psiOld itself (tile columns only) and fills the
+// coarse staging ring, which A reads (A's BQ cache): with the coarse planes in flight A needed more than 168 VGPRs.
+// B's rows d = 1 hold the tile's own column groups only (half-sweep 4 reads nothing else of them), so B is 320 threads,
+// five whole waves, and with A's 432 the workgroup has 12 waves (3 on a SIMD, 168 VGPRs) without a wave that mixes the
+// groups (A's threads beside B's in one wave spilled); A's last wave holds rows d >= 3 and skips half-sweep 2.  Every
+// expression is k_zs's, in its order: psi is bit-identical.  So is the err: a B thread keeps one (err, err1) pair per
+// 2-cell group, the accumulators of the k_zs (N = 2) thread that owned those cells, and the workgroup sums them in
+// k_zs's tree over k_zs's thread numbering.  The warm-up and the drain of a chunk grow by one step; the planes read
+// from HBM do not change (neither group loads anything for the added step).
+template <typename T>
+struct ZsSplitPost {
+    using S = ZsShape<T, false, true, true, false, 4>;
+    static_assert(S::N == 4 && S::H == 4 && S::HXG == 1 && S::NS3 == 2 && !S::PS && !S::YROLE, "POST's wide tile, 16-byte columns");
+    // A: the extended tile: the rows d <= 2 from the tile in y (every stage of A), then d = 3 (stages 0 and 1), then
+    // d = 4 (stage 0), so that its last MA threads, a wave of their own, skip half-sweep 2
+    static constexpr int G = S::G, NA = S::NT, NA2 = G * (S::TY + 4), NA3 = NA2 + 2 * G;
+    // B: the tile rows (every column group: the x-halo groups feed half-sweep 4's x neighbours), then the rows d = 1,
+    // of which half-sweep 4 reads the tile's own column groups only: GC per row, which makes B whole waves
+    static constexpr int BROWS = S::TY + 2, GC = G - 2 * S::HXG, NBT = G * S::TY, NB = NBT + 2 * GC;
+    static constexpr int NWA = NA / 64, NWB = NB / 64, MA = NA - 64 * NWA;
+    static constexpr int NW = NWA + NWB + 1, NTL = 64 * NW, WLAST = NW - 1;
+    // Wave order (bit w of BMASK: wave w is B's; the last wave holds A's last MA threads): A B A B  B A B A  A B A A'.
+    // With waves dealt to the four SIMDs in turn, every SIMD gets waves of both groups.
+    static constexpr unsigned BMASK = 0x25A;
+    static_assert(NWA == 6 && NWB == 5 && NB == 64 * NWB && MA > 0 && NW == 12, "wave order");
+    // wave w: 0 group A (every stage), 1 group B, 2 A's last wave (rows d >= 3: stages 0 and 1)
+    static __device__ __forceinline__ int wave_kind(int w) { return w == WLAST ? 2 : (int)((BMASK >> w) & 1u); }
+    static __device__ __forceinline__ int local_wave(int w)  // its index among the waves of its kind
+    {
+        const unsigned below = (1u << w) - 1u;
+        return __builtin_popcount(((BMASK >> w) & 1u) ? (BMASK & below) : (~BMASK & below));
+    }
+    static_assert(NA2 <= 64 * NWA, "A's last wave holds rows d >= 3 only");
+    static __device__ __forceinline__ int a_yrow(int t)
+    {
+        if (t < NA2) return 2 + t / G;
+        if (t < NA3) return t - NA2 < G ? 1 : S::YE - 2;
+        if (t < NA) return t - NA3 < G ? 0 : S::YE - 1;
+        return -1;
+    }
+    static __device__ __forceinline__ int b_yrow(int t)
+    {
+        if (t < NBT) return S::H + t / G;
+        return t - NBT < GC ? S::H - 1 : S::H + S::TY;
+    }
+    static __device__ __forceinline__ int b_ycol(int t) { return t < NBT ? t % G : S::HXG + (t - NBT) % GC; }
+    // LDS: stage 0 and stage 1 (2 slots each), the stage-2 ring (4), stage 3 (2), the coarse ring, the f rings
+    static constexpr int SLOT = S::SLOT, OFF1 = 2 * SLOT, OFF2 = 4 * SLOT, OFF3 = 8 * SLOT, OFFC = 10 * SLOT;
+    static constexpr int FSLOT = BROWS * S::HWE;
+    static constexpr int OFFFR = OFFC + 4 * S::CSLOT, OFFFB = OFFFR + 4 * FSLOT;
+    static constexpr size_t lds_bytes = (size_t)(OFFFB + 4 * FSLOT) * sizeof(T);
+    // the err partial's array: k_zs's threads (8-byte columns on the same tile: x halo 4, row-major, whole waves)
+    static constexpr int EG = (S::TX + 8) / 4, ENT = (EG * S::YE + 63) / 64 * 64;
+    static_assert(OFFC % 4 == 0 && S::CPAIRS <= 2 * NB, "coarse staging: two pairs per thread of B");
+    static_assert(NTL <= 1024 && NW <= 12, "too many waves for 168 VGPRs");
+    static_assert(lds_bytes + ENT * sizeof(double) <= 160 * 1024, "LDS");
+    static_assert(ENT <= 1024 && ENT - 512 <= NTL, "the sum's first level within the workgroup");
+};
+
+template <typename T, bool ERR>
+__global__ __launch_bounds__((ZsSplitPost<T>::NTL)) void k_zs_split_post(const T* __restrict__ src, const T* __restrict__ f,
+                                                                          T* __restrict__ dst, const T* old,
+                                                                          const T* __restrict__ V,
+                                                                          double* __restrict__ partials, Geo g, Geo gc,
+                                                                          Op<T, 3> op, T clc, int zc, int gz, int patch)
+{
+    using SP = ZsSplitPost<T>;
+    using S = typename SP::S;
+    constexpr int N = S::N, H = S::H, HWE = S::HWE, G = S::G, YE = S::YE, SLOT = S::SLOT, TX = S::TX, TY = S::TY;
+    using VT = Vec<T, N>;
+    using PF = ZsPrefetch<T, N>;
+    constexpr int PFD = 1, NPF = PFD + 1, UNR = 4;
+    extern __shared__ __align__(16) unsigned char zs_smem[];
+    T* const lds = reinterpret_cast<T*>(zs_smem);
+    const int tid = threadIdx.x;
+
+    const int tiles_x = g.nx / TX, tiles_y = g.ny / TY;
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile = b % (tiles_x * tiles_y);
+    const int Z0 = (b / (tiles_x * tiles_y)) * zc;
+    int tx_, ty_;
+    zs_tile_xy(tile, tiles_x, patch, tx_, ty_);
+    const int X0 = tx_ * TX, Y0 = ty_ * TY;
+    const int hw = g.hw, Hh = (int)g.H;
+    const int z0 = (int)g.z0, gnz = (int)g.gnz, cz0 = (int)gc.z0;
+    const int64_t P = g.P;
+    const int qlo = -gz, qhi = (int)g.nz - 1 + gz;  // readable local planes
+
+    // my wave's kind, my group, my thread of it and its column of the extended tile (as k_zs)
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int wk = SP::wave_kind(wv), lw = SP::local_wave(wv);
+    const bool grp_b = wk == 1;
+    const int lt = wk == 2 ? 64 * SP::NWA + lane : 64 * lw + lane;
+    const int yr_ = grp_b ? SP::b_yrow(lt) : SP::a_yrow(lt);
+    const bool on = yr_ >= 0;
+    const int gx = on ? (grp_b ? SP::b_ycol(lt) : lt % G) : 0, ye = on ? yr_ : 0;
+    const int gy = Y0 - H + ye;
+    const int m0 = gx * N;
+    ZsCol col;
+    col.lrow = ye * HWE + m0;
+    col.lym = (ye > 0 ? ye - 1 : ye) * HWE + m0;
+    col.lyp = (ye < YE - 1 ? ye + 1 : ye) * HWE + m0;
+    col.gm = (X0 - S::HX) / 2 + m0;  // global packed m of my first cell
+    col.x_first = gx == 0;
+    col.x_last = gx == G - 1;
+    col.lxm = col.x_first ? col.lrow : col.lrow - N;
+    col.lxp = col.x_last ? col.lrow : col.lrow + N;
+    const bool in_xy = on && gy >= 0 && gy < g.ny && col.gm >= 0 && col.gm < hw;
+    col.xin = true;  // (unused: cl = 0)
+    // columns outside the box load from a clamped in-plane position; their results never reach LDS or HBM
+    const int cgy = gy < 0 ? 0 : (gy >= g.ny ? g.ny - 1 : gy);
+    const int cgm = col.gm < 0 ? 0 : (col.gm > hw - N ? hw - N : col.gm);
+    const int goff = cgy * hw + cgm;  // in-plane offset (nx * ny < 2^31)
+    const bool tile_xy = on && ye >= H && ye < H + TY && gx >= S::HXG && gx < G - S::HXG;
+    // the y-halo rows load only the f their stages can use (k_zs's ZS_FHALO)
+    const int ydist = ye < H ? H - ye : (ye >= H + TY ? ye - (H + TY) + 1 : 0);
+    const bool need_f1 = !ZS_FHALO || ydist <= H - 1, need_f2 = !ZS_FHALO || ydist <= H - 2;
+    // my column in a slot of the f hand-off (B's rows: those within 1 of the tile)
+    const bool frow = on && ye >= H - 1 && ye <= H + TY;
+    const int lf = frow ? (ye - (H - 1)) * HWE + m0 : 0;
+    auto fslot = [&](int off, int q) { return lds + off + (q & 3) * SP::FSLOT + lf; };
+    const int zlo = Z0 - H;
+    const ZsDiag<T> dz = {};  // (cl = 0: unused)
+    // B's last step is p_end; A's last plane is k_zs's (p_end - 1): it loads nothing for the step the split adds
+    const int p_end = Z0 + zc + 4;
+    auto inz = [&](int q) { return z0 + q >= 0 && z0 + q < gnz; };  // inside the global box
+    auto pcl = [&](int q) { return q < qlo ? qlo : (q > qhi ? qhi : q); };
+    auto slot = [&](int off, int ns, int q) { return lds + off + (q & (ns - 1)) * SLOT; };
+    const int rowpar = (gy + z0) & 1;
+    auto par = [&](int q) { return rowpar ^ (q & 1); };
+    const VT vz = vzero<T, N>();
+
+    for (int i = tid; i < (int)(SP::lds_bytes / sizeof(T)); i += SP::NTL) lds[i] = (T)0;
+    __syncthreads();
+
+    // ---- the coarse staging ring, plane K in slot K & 3 (planes clamped to the box), as k_zs; B's threads fill it (A,
+    // which reads it, has no registers to spare for the planes in flight) ----
+    const int Ia = X0 / 2 - 8, Ja = Y0 / 2 - 3;
+    auto ckl = [&](int K) { return K < 0 ? 0 : (K >= gc.gnz ? gc.gnz - 1 : K); };
+    auto cslot = [&](int K) { return lds + SP::OFFC + (K & 3) * S::CSLOT; };
+    // my two pairs of the region: the in-plane offset of the pair's even cell (-1: none, or outside the coarse box) and
+    // the parity of I + J
+    int coff[2], cpar[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int t = lt + i * SP::NB;
+        const int J = Ja + t / (S::CI / 2), I = Ia + 2 * (t % (S::CI / 2));
+        const bool ok = grp_b && t < S::CPAIRS && J >= 0 && J < gc.ny && I >= 0 && I < gc.nx;
+        // I even: cells I and I + 1 sit at m = I / 2 of the two colour halves
+        coff[i] = ok ? J * gc.hw + (I >> 1) : -1;
+        cpar[i] = (I + J) & 1;
+    }
+    auto cload = [&](PF& r, int K) {
+        K = ckl(K);
+        const T* const pl = V + (int64_t)(K - cz0) * gc.P;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            r.cv[i].v[0] = r.cv[i].v[1] = (T)0;
+            if (coff[i] >= 0) {
+                const int ce = (cpar[i] + K) & 1;
+                r.cv[i].v[0] = pl[coff[i] + ce * (int)gc.H];
+                r.cv[i].v[1] = pl[coff[i] + (ce ^ 1) * (int)gc.H];
+            }
+        }
+    };
+    auto cstore = [&](const PF& r, int K) {
+        T* const sl = cslot(ckl(K));
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int t = lt + i * SP::NB;
+            if (t < S::CPAIRS) vstore<T, 2>(sl + 2 * t, r.cv[i]);  // pair t: cells 2t, 2t + 1 of the region
+        }
+    };
+    auto crow = [&](int K, int J, T (&c)[N + 2]) {  // cells cgm - 1 .. cgm + N of coarse row J, plane K
+        const T* const sl = cslot(ckl(K)) + (J - Ja) * S::CI + (cgm - Ia);
+        const Vec<T, N> mid = vload<T, N>(sl);
+        c[0] = vload_lds_whole<T, N>(sl - N).v[N - 1];
+#pragma unroll
+        for (int e = 0; e < N; ++e) c[e + 1] = mid.v[e];
+        c[N + 1] = vload_lds_whole<T, N>(sl + N).v[0];
+    };
+    if (grp_b) {  // the coarse planes the first fine plane needs
+        PF r;
+        const int K = (z0 + zlo) >> 1;
+        for (int k = K - 1; k <= K + 1; ++k) {
+            cload(r, k);
+            cstore(r, k);
+        }
+    }
+    __syncthreads();
+
+    // steady steps [ps, pe], as k_zs's POST: every plane a step touches (p .. p - 5) inside the box, Kn inside the coarse
+    // box, the prefetched planes readable, even z0 and Z0 and (z0 + Z0) % 4 == 0 (static parity of the plane and of the
+    // coarse plane), whole groups of UNR steps.  They end before the step the split adds.
+    int ps = zlo, pe = p_end - 1;
+    ps = ps > 6 - z0 ? ps : 6 - z0;
+    ps = ps > qlo + 4 ? ps : qlo + 4;
+    pe = pe < gnz - 2 - z0 ? pe : gnz - 2 - z0;
+    pe = pe < qhi - PFD ? pe : qhi - PFD;
+    ps += (UNR - (ps - zlo) % UNR) % UNR;
+    pe -= (pe - ps + 1) % UNR;
+    if (pe < ps || ((z0 | Z0) & 1) || ((z0 + Z0) & 3)) ps = pe = zlo - 1;
+    const std::false_type GEN;
+    const std::true_type STY;
+    // Every wave runs the same steps, whatever its kind, and each step ends in the step's one barrier: the bounds
+    // above are the workgroup's.  prefetch / step: the wave kind's; first_steady: before the first steady step.
+    auto run = [&](auto&& prefetch, auto&& first_steady, auto&& step) __attribute__((always_inline)) {
+        PF pb[NPF];
+#pragma unroll
+        for (int k = 0; k < NPF; ++k) pb[k].f1 = pb[k].f2 = vz;  // (the halo rows that skip f loads keep zeros)
+#pragma unroll
+        for (int k = 0; k < PFD; ++k) prefetch(GEN, pb[k], zlo + k);
+        int p = zlo;
+        // the steps up to plim of the group of UNR steps from p0 (p0 - zlo a multiple of UNR: ring slot k & 3, buffers
+        // k % NPF and (k + PFD) % NPF)
+        auto group = [&](auto st, int p0, int plim) __attribute__((always_inline)) {
+            zs_unroll<UNR>([&](auto kk) __attribute__((always_inline)) {
+                constexpr int k = decltype(kk)::value;
+                if (p0 + k <= plim) {
+                    step(st, std::integral_constant<int, (k & 3)>(), pb[k % NPF], pb[(k + PFD) % NPF], p0 + k);
+                    lds_barrier();
+                }
+            });
+        };
+        for (; p < ps; p += UNR) group(GEN, p, p + UNR);
+        if (p <= pe) first_steady(p);
+        for (; p <= pe; p += UNR) group(STY, p, p + UNR);  // (whole groups: the bound tests fold away)
+        for (; p <= p_end; p += UNR) group(GEN, p, p_end);
+    };
+
+    // ---- group A: stage 0 with the coarse correction, half-sweeps 1 and 2 (k_zs's) ----
+    const T* const src_black = src + Hh;
+    auto prefetch_a = [&](auto st, PF& r, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        if (ST) {
+            const int64_t pP = (int64_t)p * P;
+            r.u = gload<T, N, kZsNTL>(src_black + pP + goff);
+            if (need_f1) r.f1 = gload<T, N, kZsNTL>(f + (pP - P) + goff);
+            if (need_f2) r.f2 = gload<T, N, kZsNTL>(f + (pP - 2 * P) + Hh + goff);
+        } else {
+            r.u = gload<T, N, kZsNTL>(src_black + (int64_t)pcl(p) * P + goff);
+            if (need_f1) r.f1 = gload<T, N, kZsNTL>(f + (int64_t)pcl(p - 1) * P + goff);
+            if (need_f2) r.f2 = gload<T, N, kZsNTL>(f + (int64_t)pcl(p - 2) * P + Hh + goff);
+        }
+    };
+    // W0: A0 black at p-2 .. p; W1: A1 red at p-3 .. p-1 (plane q in slot (q - zlo) & 3; every step knows its slot
+    // offset at compile time, as k_zs)
+    VT W0[4], W1[4];
+    // the per-lane half of the interior test of the coarse correction (lanes without a column do not vote)
+    const bool corr_lane = (cgy >> 1) + ((cgy & 1) ? 1 : -1) >= 0 && (cgy >> 1) + ((cgy & 1) ? 1 : -1) < gc.ny && cgm > 0 &&
+                           cgm + N < gc.nx;
+    const bool corr_fast = __all(!on || corr_lane);
+    // steady steps: BQ[K & 1][q][e] = zs_bq of coarse plane K for the black cells of the fine planes of parity 1 ^ q (see
+    // k_zs)
+    T BQ[2][2][N];
+    // (each group's rings start from zeros in its own branch below: nothing of the other group's stays live in it)
+    auto init_a = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) W0[i] = W1[i] = vz;
+#pragma unroll
+        for (int i = 0; i < 2 * 2 * N; ++i) (&BQ[0][0][0])[i] = (T)0;
+    };
+    const int bq_J = cgy >> 1;
+    int bq_Jn = (cgy & 1) ? bq_J + 1 : bq_J - 1;
+    const bool bq_oy = bq_Jn < 0 || bq_Jn >= gc.ny;
+    if (bq_oy) bq_Jn = bq_J;
+    auto bq_fill = [&](T (&bq)[2][N], int K) __attribute__((always_inline)) {
+        const int cp = cgy & 1;
+        T c0[N + 2], c1[N + 2];
+        crow(K, bq_J, c0);
+        crow(K, bq_Jn, c1);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) zs_bq<T, N>(bq[q], c0, c1, q ^ cp, cgm, gc.nx, bq_oy, clc, corr_fast);
+    };
+    auto first_steady_a = [&](int p) __attribute__((always_inline)) {
+        // the first steady step (even, K & 1 == 0) reads coarse planes K and K - 1
+        const int K = (z0 + p) >> 1;
+        bq_fill(BQ[0], K);
+        bq_fill(BQ[1], K - 1);
+    };
+    // full: every stage of A (false: A's last wave, rows d >= 3: stages 0 and 1)
+    auto step_a = [&](auto st, auto rt, auto full, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value, FULL = decltype(full)::value;
+        constexpr int RS = decltype(rt)::value;  // (p - zlo) & 3
+        auto sl = [](int k) constexpr { return (RS - k) & 3; };  // ring slot of plane p - k
+        if (!ST && p >= p_end) return;  // the step the split adds: nothing of A's would be read (cur holds no new plane)
+        if (ST) p = (p & ~1) | ((H + RS) & 1);  // steady: Z0 even, so p's parity is zlo's plus RS
+        const int zz0 = ST ? (z0 & ~1) : z0;
+        zs_hold<T, N>(cur.u);
+        zs_hold<T, N>(cur.f1);
+        zs_hold<T, N>(cur.f2);
+        asm volatile("" ::: "memory");
+        if (ST || p + PFD <= p_end - 1) prefetch_a(st, nxt, p + PFD);
+        ZsNb<T, N> n1, n2;
+        // ---- stage 0: black cells of plane p ----
+        VT a0 = cur.u;
+        if constexpr (ST) {
+            // (z0 + Z0) % 4 == 0 in steady steps: K & 1 and p & 1 are static
+            constexpr int KS = (RS >> 1) & 1, Q = 1 ^ (RS & 1);
+            if constexpr ((RS & 1) != 0) bq_fill(BQ[KS ^ 1], ((zz0 + p) >> 1) + 1);
+            const T w0 = (T)0.75, w1 = (T)0.25;
+#pragma unroll
+            for (int e = 0; e < N; ++e) a0.v[e] = a0.v[e] + (w0 * BQ[KS][Q][e] + w1 * BQ[KS ^ 1][Q][e]);
+        } else if (inz(p)) {
+            const int J = cgy >> 1, K = (zz0 + p) >> 1;
+            int Jn = (cgy & 1) ? J + 1 : J - 1;
+            int Kn = ((zz0 + p) & 1) ? K + 1 : K - 1;
+            const bool oy = Jn < 0 || Jn >= gc.ny, oz = Kn < 0 || Kn >= gc.gnz;
+            if (oy) Jn = J;
+            if (oz) Kn = K;
+            ZsCoarse<T, N> cc;
+            crow(K, J, cc.c00);
+            crow(K, Jn, cc.c10);
+            crow(Kn, J, cc.c01);
+            crow(Kn, Jn, cc.c11);
+            zs_correct<T, N, 1>(a0, cc, 1 ^ ((cgy + zz0 + p) & 1), cgm, gc.nx, oy, oz, clc,
+                                __all(!oy && !oz && cgm > 0 && cgm + N < gc.nx));
+        }
+        if (!ST && !inz(p)) a0 = vz;
+        W0[sl(0)] = a0;
+        // ---- half-sweeps 1 and 2 on planes p - 1 (red) and p - 2 (black) ----
+        zs_nb_load<T, N>(n1, slot(0, 2, p - 1), col);
+        VT o1 = zs_relax<T, N, true, ST>(W0[sl(2)], W0[sl(1)], W0[sl(0)], n1, cur.f1, col, par(p - 1), 0, g.nx, op, dz);
+        if (!ST && !inz(p - 1)) o1 = vz;
+        W1[sl(1)] = o1;
+        VT o2 = vz;
+        if constexpr (FULL) {
+            zs_nb_load<T, N>(n2, slot(SP::OFF1, 2, p - 2), col);
+            o2 = zs_relax<T, N, true, ST>(W1[sl(3)], W1[sl(2)], W1[sl(1)], n2, cur.f2, col, 1 ^ par(p - 2), 0, g.nx, op, dz);
+            if (!ST && !inz(p - 2)) o2 = vz;
+        }
+        if (in_xy) {  // (slots no stage of this step reads; columns outside the box stay 0)
+            vstore<T, N>(slot(0, 2, p) + col.lrow, a0);
+            vstore<T, N>(slot(SP::OFF1, 2, p - 1) + col.lrow, o1);
+            // (B reads its own column of it in the next step, the neighbours in the step after)
+            if constexpr (FULL) vstore<T, N>(slot(SP::OFF2, 4, p - 2) + col.lrow, o2);
+            if (FULL && frow) {  // B reads them three steps later (stage 3: red f of plane p - 4, stage 4: black f of p - 5)
+                vstore<T, N>(fslot(SP::OFFFR, p - 1), cur.f1);
+                vstore<T, N>(fslot(SP::OFFFB, p - 2), cur.f2);
+            }
+        }
+    };
+
+    // ---- group B: half-sweeps 3 and 4, the err, the smoothed plane ----
+    auto prefetch_b = [&](auto st, PF& r, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        const int zz0 = ST ? (z0 & ~1) : z0;
+        // fine plane 2m + 1 is the first to need coarse plane m + 1; it is loaded with the prefetch of plane 2m and put
+        // in the ring at the top of step 2m (none for the step the split adds: A corrects no plane there)
+        if ((ST || p < p_end) && ((zz0 + p) & 1) == 0) cload(r, ((zz0 + p) >> 1) + 1);
+        if (ERR && tile_xy) {  // psiOld of plane p - 5 (the plane step p finalizes), for the tile's own columns only
+            const T* dp = old + (ST ? (int64_t)p * P - 5 * P : (int64_t)pcl(p - 5) * P);
+            r.o0 = gload<T, N, kZsNTO>(dp + goff);
+            r.o1 = gload<T, N, kZsNTO>(dp + Hh + goff);
+        }
+    };
+    // W3: A3 red at p-6 .. p-4 (A2's planes p-5 .. p-3 of my column come from the stage-2 ring every step: its fourth
+    // slot is the one A fills meanwhile, and B has no registers to keep them in)
+    VT W3[4];
+    // err[j], err1[j]: the accumulators of k_zs's thread that owns my cells 2j, 2j + 1 of each colour
+    double err[2], err1[2];
+    double esum[2] = {0.0, 0.0};  // err[j] + err1[j] after the last step
+    auto step_b = [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+        constexpr bool ST = decltype(st)::value;
+        constexpr int RS = decltype(rt)::value;  // (p - zlo) & 3
+        auto sl = [](int k) constexpr { return (RS - k) & 3; };  // ring slot of plane p - k
+        if (ST) p = (p & ~1) | ((H + RS) & 1);
+        const int zz0 = ST ? (z0 & ~1) : z0;
+        if (ERR) {
+            zs_hold<T, N>(cur.o0);
+            zs_hold<T, N>(cur.o1);
+        }
+        zs_hold<T, 2>(cur.cv[0]);
+        zs_hold<T, 2>(cur.cv[1]);
+        asm volatile("" ::: "memory");
+        // the coarse plane cur's prefetch loaded (A first reads it one step on; the slot it replaces was last read three
+        // steps back)
+        if ((ST || p < p_end) && ((zz0 + p) & 1) == 0) cstore(cur, ((zz0 + p) >> 1) + 1);
+        if (ST || p + PFD <= p_end) prefetch_b(st, nxt, p + PFD);
+        ZsNb<T, N> n3, n4;
+        // ---- half-sweep 3 on plane p - 4: A's stage-2 planes p - 5 .. p - 3, the newest written one step ago ----
+        const VT w2l = vload<T, N>(slot(SP::OFF2, 4, p - 5) + col.lrow), w2c = vload<T, N>(slot(SP::OFF2, 4, p - 4) + col.lrow),
+                 w2r = vload<T, N>(slot(SP::OFF2, 4, p - 3) + col.lrow);
+        const VT fr = vload<T, N>(fslot(SP::OFFFR, p - 4));  // red f of plane p - 4
+        zs_nb_load<T, N>(n3, slot(SP::OFF2, 4, p - 4), col);
+        VT o3 = zs_relax<T, N, true, ST>(w2l, w2c, w2r, n3, fr, col, par(p - 4), 0, g.nx, op, dz);
+        if (!ST && !inz(p - 4)) o3 = vz;
+        if (in_xy) vstore<T, N>(slot(SP::OFF3, 2, p - 4) + col.lrow, o3);
+        W3[sl(4)] = o3;
+        // ---- half-sweep 4 on plane p - 5 ----
+        const VT fb = vload<T, N>(fslot(SP::OFFFB, p - 5));  // black f of plane p - 5
+        zs_nb_load<T, N>(n4, slot(SP::OFF3, 2, p - 5), col);
+        VT o4 = zs_relax<T, N, true, ST>(W3[sl(6)], W3[sl(5)], W3[sl(4)], n4, fb, col, 1 ^ par(p - 5), 0, g.nx, op, dz);
+        if (!ST && !inz(p - 5)) o4 = vz;
+        // ---- the smoothed plane p - 5: red final after stage 3, black after stage 4 (the chunk test is wave-uniform) ----
+        const int q = p - 5;
+        if (q >= Z0 && q < Z0 + zc && tile_xy) {
+            if (ERR) {
+#pragma unroll
+                for (int e = 0; e < N; ++e) {
+                    // (psi - psiOld)^2 in fp64, fused multiply-add, in the order of k_zs's thread of the pair
+                    const double d0 = (double)W3[sl(5)].v[e] - (double)cur.o0.v[e];
+                    const double d1 = (double)o4.v[e] - (double)cur.o1.v[e];
+                    err[e >> 1] = __builtin_fma(d0, d0, err[e >> 1]);
+                    err1[e >> 1] = __builtin_fma(d1, d1, err1[e >> 1]);
+                }
+            }
+            T* dp = dst + (int64_t)q * P;
+            gstore<T, N, kZsNTS>(dp + goff, W3[sl(5)]);
+            gstore<T, N, kZsNTS>(dp + Hh + goff, o4);
+        }
+    };
+
+    if (wk == 0) {
+        init_a();
+        run(prefetch_a, first_steady_a, [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+            step_a(st, rt, STY, cur, nxt, p);
+        });
+    } else if (wk == 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) W3[i] = vz;
+        err[0] = err[1] = err1[0] = err1[1] = 0.0;
+        run(prefetch_b, [](int) {}, step_b);
+        esum[0] = err[0] + err1[0];
+        esum[1] = err[1] + err1[1];
+    } else {
+        init_a();
+        run(prefetch_a, first_steady_a, [&](auto st, auto rt, const PF& cur, PF& nxt, int p) __attribute__((always_inline)) {
+            step_a(st, rt, GEN, cur, nxt, p);
+        });
+    }
+    if constexpr (ERR) {
+        // k_zs's workgroup sum (block_partial_t over its ENT threads): thread row x EG + column group holds err + err1
+        // of its cells; my pair j is column group 2 gx - 1 + j of k_zs's row
+        __shared__ double red[SP::ENT];
+        for (int i = tid; i < SP::ENT; i += SP::NTL) red[i] = 0.0;
+        __syncthreads();
+        // (my row and column group again, from the thread index: nothing of them stays live through A's loops)
+        int t2 = tid;
+        asm volatile("" : "+v"(t2));
+        const int w2 = t2 >> 6, l2 = SP::local_wave(w2) * 64 + (t2 & 63);
+        const int y2 = SP::b_yrow(l2), x2 = SP::b_ycol(l2);
+        if (SP::wave_kind(w2) == 1 && y2 >= H && y2 < H + TY && x2 >= S::HXG && x2 < G - S::HXG) {
+            red[y2 * SP::EG + 2 * x2 - 1] = esum[0];
+            red[y2 * SP::EG + 2 * x2] = esum[1];
+        }
+        __syncthreads();
+        for (int w = 512; w > 0; w >>= 1) {
+            if (tid < w && tid + w < SP::ENT) red[tid] += red[tid + w];
+            __syncthreads();
+        }
+        if (tid == 0) partials[blockIdx.x] = red[0];
+    }
 }
 
 // ---- y-streamed temporally blocked smoothing (2D, red/black 2+2) -------------------------------
@@ -4956,6 +5425,8 @@ FusedTuning fused_tuning_from_env()
     if (const char* v = std::getenv("MGP_ZS_SPLIT")) t.split = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_ZS_SPLIT_CL")) t.split_cl = std::atoi(v) != 0;
     if (const char* v = std::getenv("MGP_ZPOST_PRE")) t.zpost_pre = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MGP_ZS_SPLIT_POST")) t.split_post = std::atoi(v) != 0;
+    if (const char* v = std::getenv("MGP_ZS_SPLIT_POST_MIN_CELLS")) t.split_post_min_cells = std::max<int64_t>(0, std::atoll(v));
     if (const char* v = std::getenv("MGP_STAMP_R")) t.stamp_r = std::atoi(v) != 0;
     return t;
 }
@@ -5025,6 +5496,26 @@ static hipError_t zs_split_cl_launch(const FusedArgs& a, hipStream_t s)
     k_zs_split_cl<float><<<nb, SP::NTL, SP::lds_bytes, s>>>((const float*)a.f, (float*)a.dst, (float*)a.R, a.g, a.gc, op, a.zc,
                                                            a.ghost,
                                                            zs_patch(a.tu.patch_pre, a.g.nx / S::TX, a.g.ny / S::TY, nb));
+    return hipGetLastError();
+}
+
+// POST with trilinear prolongation, fp32, cl = 0, on the wide tile: the stage-split kernel (fused_dispatch: levels of
+// at least FusedTuning::split_post_min_cells cells).  Its tile, its workgroups and their order are k_zs's.
+template <bool ERR>
+static hipError_t zs_split_post_launch(const FusedArgs& a, hipStream_t s)
+{
+    using SP = ZsSplitPost<float>;
+    using S = SP::S;
+    const Op<float, 3> op = make_op<float, 3>(a.h, a.cl);
+    const unsigned nb = (unsigned)((a.g.nx / S::TX) * (a.g.ny / S::TY) * (a.g.nz / a.zc));
+    if (a.info) {  // rocprofv3's spelling of the instantiation
+        std::snprintf(a.info->name, sizeof a.info->name, "k_zs_split_post<float, %s>", tf(ERR));
+        a.info->grid = (int64_t)nb * SP::NTL;
+    }
+    k_zs_split_post<float, ERR><<<nb, SP::NTL, SP::lds_bytes, s>>>(
+        (const float*)a.src, (const float*)a.f, (float*)a.dst, (const float*)(a.old ? a.old : a.dst), (const float*)a.V,
+        a.partials, a.g, a.gc, op, (float)a.clc, a.zc, a.ghost,
+        zs_patch(a.tu.patch_post, a.g.nx / S::TX, a.g.ny / S::TY, nb));
     return hipGetLastError();
 }
 
@@ -5098,6 +5589,10 @@ static hipError_t fused_dispatch(const FusedArgs& a, hipStream_t s)
     if (a.pre) return a.linear ? zs_launch<T, true, 1, false, CLZ>(a, s) : zs_launch<T, true, 0, false, CLZ>(a, s);
     if constexpr (std::is_same<T, float>::value && CLZ) {
         if (zs_wide(4, a.g, true, a.tu)) {
+            static_assert(ZsSplitPost<float>::S::TX == ZsTile<float>::TXPOST_W && ZsSplitPost<float>::S::TY == ZsTile<float>::TYPOST_W,
+                          "the split POST runs on the wide tile");
+            if (a.linear && a.tu.split_post && (int64_t)a.g.nx * a.g.ny * a.g.nz >= a.tu.split_post_min_cells)
+                return err ? zs_split_post_launch<true>(a, s) : zs_split_post_launch<false>(a, s);
             if (a.linear)
                 return err ? zs_launch<T, false, 1, true, CLZ, true>(a, s) : zs_launch<T, false, 1, false, CLZ, true>(a, s);
             return err ? zs_launch<T, false, 0, true, CLZ, true>(a, s) : zs_launch<T, false, 0, false, CLZ, true>(a, s);
@@ -5227,6 +5722,9 @@ static hipError_t fused_attr()
         const int w = (int)ZsSplit<float>::lds_bytes;
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, false>, A, w);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split<float, true>, A, w);
+        const int wp = (int)ZsSplitPost<float>::lds_bytes;
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split_post<float, true>, A, wp);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_zs_split_post<float, false>, A, wp);
     }
     if constexpr (std::is_same<T, float>::value && !CLZ) {
         if (e == hipSuccess)
