@@ -1,6 +1,6 @@
 // mgp_blk2.hip — the tiled smoothing phases of two consecutive small 2D levels in one launch (round 6).
 //
-// k_blk (mgp_kernels.hip) runs a small level's PRE (nu1 red/black sweeps, calcResidual, reduceResidual:
+// k_blk (mgp_blk.hip) runs a small level's PRE (nu1 red/black sweeps, calcResidual, reduceResidual:
 // cpu.lua:40-54, 108-135) as one launch per level; below 1024^2 a launch costs more than its work.  k_blk2_pre
 // runs PRE of level l AND of level l + 1 in one launch (V-cycle, cpu.lua:138-139: the coarse level's PRE follows the
 // fine level's restriction directly).  A workgroup owns a B x B tile of level l + 1 (2B x 2B of level l):

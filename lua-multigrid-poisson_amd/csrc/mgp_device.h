@@ -1,5 +1,6 @@
-// mgp_device.h — device primitives shared by the kernel translation units (mgp_kernels.hip, mgp_fw.hip):
-// 16-byte vectors, the Markstein division, the level operator Op, the packed red/black index, the XCD remap.
+// mgp_device.h — device primitives shared by the kernel translation units (mgp_kernels.hip, mgp_zs.hip, mgp_tail.hip,
+// mgp_blk.hip, mgp_gslex.hip, mgp_fw.hip, ...): 16-byte vectors, the Markstein division, the level operator Op, the
+// packed red/black index, the XCD remap, the workgroup sums, the LDS barrier, and the launchers' MGP_REAL / tf.
 // Everything is internal to each translation unit (anonymous namespace).
 #pragma once
 #include "mgp_internal.h"
@@ -290,6 +291,15 @@ __device__ __forceinline__ int xcd_remap(int b, int nblocks)
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// Element-wise kernels over every packed slot of a level run grid-stride over at most kMaxBlocks
+// workgroups: a 4096 x 4096 x 512 slab has 8.6e9 slots, past the 2^32 work-items one launch allows.
+constexpr unsigned kMaxBlocks = 1u << 20;
+inline unsigned nblk_gs(int64_t n)
+{
+    const int64_t b = (n + kBlock - 1) / kBlock;
+    return (unsigned)(b < (int64_t)kMaxBlocks ? (b > 0 ? b : 1) : kMaxBlocks);
+}
+
 template <typename T>
 __device__ __forceinline__ void block_partial(double acc, double* partials)
 {
@@ -303,6 +313,30 @@ __device__ __forceinline__ void block_partial(double acc, double* partials)
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
+// Fixed-order workgroup sum of one double per thread (NTL threads, any count <= 1024).
+template <int NTL>
+__device__ __forceinline__ void block_partial_t(double acc, double* partials)
+{
+    __shared__ double red[NTL];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w && (int)threadIdx.x + w < NTL) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations, not for its
+// outstanding global loads (the next step's prefetch stays in flight across the barrier).
+__device__ __forceinline__ void lds_barrier()
+{
+#ifdef ZS_NOBAR  // timing experiment only: results are wrong
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#else
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#endif
+}
 
 // The full weighting's per-axis combination ((a + wb b) + wc c) + d (weights 1, 3, 3, 1; wb / wc = 3 - c_l
 // next to a face of the coarse box)
@@ -365,5 +399,20 @@ __device__ __forceinline__ T prolong_eval(const Get& get, const Geo& gc, T cl, i
     return v;
 }
 
+// "true" / "false": rocprofv3's spelling of a bool template argument (LaunchInfo::name)
+inline const char* tf(bool v) { return v ? "true" : "false"; }
+
 }  // namespace
 }  // namespace mgp
+
+// BODY with T = the real type of rb (4: float, 8: double)
+#define MGP_REAL(rb, BODY)             \
+    do {                               \
+        if (rb == 8) {                 \
+            using T = double;          \
+            BODY;                      \
+        } else {                       \
+            using T = float;           \
+            BODY;                      \
+        }                              \
+    } while (0)

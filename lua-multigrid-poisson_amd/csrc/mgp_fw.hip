@@ -9,7 +9,7 @@
 // in an LDS ring of three planes, evaluates r on the tile plus a one-cell ring into LDS, and reduces r along x
 // and y to the coarse cells (fw_axis, then the y accumulation: fw_eval's `ay`); four consecutive `ay` planes give
 // one coarse plane (fw_eval's `az`).  Per fine cell it reads u and f once (+ the tile halos, mostly from L2) and
-// writes R / 2^d: 2 + 2^-d reals.  Every expression and its order is residual_at's / fw_eval's (mgp_kernels.hip),
+// writes R / 2^d: 2 + 2^-d reals.  Every expression and its order is residual_at's / fw_eval's (mgp_cell.h),
 // so R is bit-identical to the two-pass path and to the oracle (restrict_fw in oracle/mgp_oracle_impl.h).
 #include "mgp_device.h"
 

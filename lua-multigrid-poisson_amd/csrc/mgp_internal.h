@@ -1,5 +1,8 @@
-// mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4
-// kernels (mgp_kernels.hip).  Not part of the public ABI (include/mgpoisson.h is).
+// mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4 kernel units:
+// mgp_kernels.hip (one launch per piece; k_zs's stage-split variants and the 2D k_ys), mgp_zs.hip / mgp_zs_f64.hip (k_zs, the fused
+// phases' planning and dispatch), mgp_tail.hip (coarse tail), mgp_blk.hip / mgp_blk2.hip (tiled phases), mgp_gslex.hip,
+// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip.  The last block holds what the kernel units
+// call in each other.  Not part of the public ABI (include/mgpoisson.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -319,5 +322,24 @@ hipError_t launch_gslex_sweep(int rb, int dim, void* u, const void* f, Geo g, do
 hipError_t launch_stall(const int* flag, double max_s, hipStream_t s);
 
 constexpr int kSumBlocks = 1024;
+
+// ---- between the kernel units; not used by mgp_api.cpp ---------------------------------------------------------
+// An anonymous-namespace kernel cannot be named from another unit, so each unit launches its own kernels and raises
+// their dynamic-LDS limit itself; prepare_kernels (mgp_zs.hip) chains these with blk2_attr.
+hipError_t zs_split_attr(int rb);  // mgp_kernels.hip
+hipError_t zs_attr_f64();          // mgp_zs_f64.hip (k_zs's fp64 instantiations; the fp32 ones: mgp_zs.hip)
+hipError_t tail_attr(int rb);      // mgp_tail.hip
+hipError_t blk_attr(int rb);       // mgp_blk.hip
+// fused_dispatch's (mgp_zs.hip) stage-split launches (mgp_kernels.hip), fp32: PRE on a cl = 0 level (from src, or from
+// a fresh zero guess when it is null), PRE on a cl != 0 level from a fresh zero guess, POST (err with partials)
+hipError_t launch_zs_split(const FusedArgs& a, hipStream_t s);
+hipError_t launch_zs_split_cl(const FusedArgs& a, hipStream_t s);
+hipError_t launch_zs_split_post(const FusedArgs& a, hipStream_t s);
+// launch_fused on a 2D level (k_ys, mgp_kernels.hip), and its segment planning for fused_supported / fused_zc /
+// fused_blocks
+hipError_t launch_fused_f64(const FusedArgs& a, hipStream_t s);  // launch_fused on a 3D fp64 level (mgp_zs_f64.hip)
+hipError_t launch_fused_2d(int rb, const FusedArgs& a, hipStream_t s);
+int ys_rows(const Geo& g, const FusedTuning& tu);
+int ys_tx(int rb, const Geo& g, const FusedTuning& tu);
 
 }  // namespace mgp

@@ -276,6 +276,15 @@ FUSED_CONFIGS = [
     dict(n=(128, 64, 32), real="double", prolong="pc", coarse_bc="zero"),
     dict(n=(64, 128, 64), real="double", prolong="linear", coarse_bc="consistent", coarse_init="warm"),
     dict(n=(64, 32, 128), real="float", prolong="pc", coarse_bc="consistent", err_mode=0),
+    # instantiations of k_zs / k_zs_split_post that no other case launches: the narrow POST with injection and err on
+    # level 0 and, on the fused cl != 0 level 1, without; the wide linear POST without err on k_zs and (every level
+    # size on the stage-split kernel) on k_zs_split_post; fp64 level 1 with cl = 0 (the smoothing-only PRE before the
+    # full weighting from a fresh guess, the linear POST without err) and with cl != 0 (POST with injection)
+    dict(n=(128, 64, 64), real="float", prolong="pc", coarse_bc="consistent", wide="0"),
+    dict(n=(128, 32, 32), real="float", prolong="linear", coarse_bc="consistent", err_mode=0),
+    dict(n=(128, 32, 32), real="float", prolong="linear", coarse_bc="consistent", err_mode=0, split_post_min="0"),
+    dict(n=(128, 64, 64), real="double", prolong="linear", coarse_bc="zero", restriction="full_weighting"),
+    dict(n=(128, 64, 64), real="double", prolong="pc", coarse_bc="consistent"),
 ]
 
 
@@ -285,6 +294,8 @@ def test_fused_phases_match_oracle(cfg, monkeypatch):
     half-sweep vs the C oracle: psi bit-identical on every level; err to summation order."""
     cfg = dict(cfg)
     monkeypatch.setenv("MGP_ZS_WIDE", cfg.pop("wide", "1"))
+    if "split_post_min" in cfg:  # the smallest level (cells) that takes k_zs_split_post (default 2^27)
+        monkeypatch.setenv("MGP_ZS_SPLIT_POST_MIN_CELLS", cfg.pop("split_post_min"))
     kw = dict(dim=3, smoother="rbgs", nu1=2, nu2=2, **cfg)
     monkeypatch.setenv("MGP_FUSED_MIN_CELLS", "65536")
     monkeypatch.setenv("MGP_FUSED", "1")
@@ -338,6 +349,23 @@ YS_CONFIGS = [
     dict(n=(2048, 2048, 1), real="float", prolong="linear", coarse_bc="consistent", cycle="F", rows="16"),
     dict(n=(1024, 512, 1), real="double", prolong="linear", coarse_bc="zero", err_mode=0, half="0"),
     dict(n=(1024, 1024, 1), real="double", prolong="pc", coarse_bc="consistent", half="1"),
+    # instantiations of k_ys that no other case launches.  fp32, cl = 0: POST without err on full-width segments
+    # (injection; linear, after the smoothing-only PRE before the full weighting); POST with injection on half-width
+    # segments, with err (level 0) and without (level 1)
+    dict(n=(1024, 512, 1), real="float", prolong="pc", coarse_bc="zero", err_mode=0, half="0"),
+    dict(n=(1024, 512, 1), real="float", prolong="linear", coarse_bc="consistent", restriction="full_weighting",
+         err_mode=0, half="0"),
+    dict(n=(1024, 512, 1), real="float", prolong="pc", coarse_bc="zero", half="1"),
+    # fp32, cl != 0 (level 1): full-width segments (1024 of a 2048-wide box) with the average and injection, and with
+    # the full weighting and linear prolongation; half-width segments with injection
+    dict(n=(2048, 512, 1), real="float", prolong="pc", coarse_bc="consistent", half="0"),
+    dict(n=(2048, 512, 1), real="float", prolong="linear", coarse_bc="consistent", restriction="full_weighting", half="0"),
+    dict(n=(1024, 512, 1), real="float", prolong="pc", coarse_bc="consistent", half="1"),
+    # fp64: POST with injection and no err on full-width (level 0) and half-width (level 1, cl = 0) segments; the
+    # full weighting's PRE and the linear POST on full-width segments of level 0 (cl = 0) and level 1 (cl != 0)
+    dict(n=(512, 512, 1), real="double", prolong="pc", coarse_bc="zero", err_mode=0, half="0"),
+    dict(n=(512, 512, 1), real="double", prolong="pc", coarse_bc="zero", half="1"),
+    dict(n=(1024, 512, 1), real="double", prolong="linear", coarse_bc="consistent", restriction="full_weighting", half="0"),
 ]
 
 
