@@ -232,6 +232,7 @@ struct mgp_ctx {
     bool dry = false;
     bool nb_comm = false;  // non-blocking communicators (mgp_group_create): every call is polled to completion
     mgp::FusedTuning tu;   // tile settings of the temporally blocked phases (env, snapshot at creation)
+    mgp::PieceTuning pt;   // kernel forms of the per-piece launches (env, snapshot at creation)
     bool resfw = true;     // the full weighting's residual + restriction as one pass (MGP_RESFW=0: two passes)
     bool bres = true;      // the last pre black half-sweep fused with residual + restriction (MGP_BRES=0: apart)
     // whole red/black sweeps of levels below the finest in one pass (MGP_RBSWEEP=1; off by default: at 128^3 11.5 us
@@ -816,7 +817,7 @@ int half(mgp_ctx* c, int l, int color, char* other, char* dst, const char* old, 
     TRY(timed_begin(c, old ? -1 : l, &e));
     HIP_TRY(c, mgp::launch_half_sweep(c->rk, c->o.dim, l == 0, color, c->ui(L, other) - back, c->ui(L, L.f) - back,
                                       c->ui(L, dst) - back, old ? c->ui(L, (char*)old) : nullptr, c->d_part + part_off,
-                                      g, h, cl, c->use_gs, c->s));
+                                      g, h, cl, c->use_gs, c->pt, c->s));
     TRY(timed_end(c, e, MGP_TIMING_HALF_SWEEP, 1.5 * c->rb * (double)level_cells(L)));
     return MGP_OK;
 }
@@ -904,7 +905,7 @@ int smooth(mgp_ctx* c, int l, int sweeps, double h, bool want_err = false, bool 
             !(black_later && sw == sweeps - 1)) {
             // the whole sweep in one pass into t; its red cells are needed only if no red half-sweep follows
             HIP_TRY(c, mgp::launch_rb_sweep(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), c->ui(L, L.t), L.g, h, cl,
-                                            sw == sweeps - 1, c->s));
+                                            sw == sweeps - 1, c->pt, c->s));
             std::swap(L.u, L.t);
             L.ghost_ok = !L.p.dist;
             L.ghost_zero = false;
@@ -1052,7 +1053,7 @@ int black_residual_restrict(mgp_ctx* c, int l, double h)
     const Geo gc = coarse_view(L, C, &zc);
     char* R = c->ui(C, C.f) + (size_t)(zc * C.g.P) * c->rb;
     HIP_TRY(c, mgp::launch_black_residual_restrict(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), R, L.g, gc, h,
-                                                   coarse_coef(c->o.coarse_bc, l), c->s));
+                                                   coarse_coef(c->o.coarse_bc, l), c->pt, c->s));
     L.ghost_ok = true;
     L.ghost_zero = false;
     C.fghost_ok = !C.p.dist;
@@ -1070,7 +1071,7 @@ int residual_restrict(mgp_ctx* c, int l, double h)
     const Geo gc = coarse_view(L, C, &zc);
     char* R = c->ui(C, C.f) + (size_t)(zc * C.g.P) * c->rb;
     HIP_TRY(c, mgp::launch_residual_restrict(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), R, L.g, gc, h,
-                                             coarse_coef(c->o.coarse_bc, l), c->s));
+                                             coarse_coef(c->o.coarse_bc, l), c->pt, c->s));
     C.fghost_ok = !C.p.dist;
     if (L.p.dist && !C.p.dist) TRY(gather_coarse_rhs(c, L, C, R));
     return MGP_OK;
@@ -1763,7 +1764,7 @@ int one_cycle(mgp_ctx* c, double* dst)
     if (c->o.err_mode && !fuse) {
         Level& L0 = c->lev[0];
         HIP_TRY(c, mgp::launch_sqdiff_sum(c->rk, c->ui(L0, L0.u), c->psi_old, L0.g.P * L0.g.nz, c->d_part, dst, c->s,
-                                          c->err_ctr));
+                                          c->err_ctr, &L0.g));
     }
     if (c->o.err_mode && c->multi()) {
         comm_log(c, 2, 0, 0, 1, (int64_t)sizeof(double));
@@ -1998,6 +1999,7 @@ static void host_setup(mgp_ctx* c, const mgp_opts& o, const std::vector<LevelPla
         c->stall_at = vs ? std::max(0LL, std::atoll(vs)) : 0;
     }
     c->tu = mgp::fused_tuning_from_env();
+    c->pt = mgp::piece_tuning_from_env();
     c->G = o.dim == 3 ? mgp::kGhost3D : 0;  // widened below when a distributed level is fused
     {
         const char* v = std::getenv("MGP_FRESH");
@@ -2920,7 +2922,8 @@ int mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* frob)
     if (!c->d_metrics) HIP_TRY(c, hipMalloc(&c->d_metrics, sizeof(double) * (3 * mgp::kSumBlocks + 3)));
     const Level& L0 = c->lev[0];
     double* out = c->d_metrics + 3 * mgp::kSumBlocks;
-    HIP_TRY(c, mgp::launch_metrics(c->rb, c->ui(L0, L0.u), c->metrics_old, L0.g.P * L0.g.nz, c->d_metrics, out, c->s));
+    HIP_TRY(c, mgp::launch_metrics(c->rb, c->ui(L0, L0.u), c->metrics_old, L0.g.P * L0.g.nz, c->d_metrics, out, c->s,
+                                   &L0.g));
     WaitScope w(c);  // the all-reduce and the read-back after it wait for the peers
     if (c->multi()) {
         if (c->lb)

@@ -572,14 +572,10 @@ bool bres_supported(int rb, const Geo& g)
     return (rb == 4 || rb == 8) && g.nx >= 2 && g.ny >= 2 && (g.z0 & 1) == 0;
 }
 
-// cells per thread of the vector forms (MGP_BRES_VN, read once: 0 = the scalar forms, 1 / 2 / 4; default one 16-byte
-// vector) on levels whose half rows hold a whole number of them
-static int bres_vn(int rb, const Geo& g)
+// cells per thread of the vector forms (PieceTuning::bres_vn, MGP_BRES_VN: 0 = the scalar forms, 1 / 2 / 4; default one
+// 16-byte vector) on levels whose half rows hold a whole number of them
+static int bres_vn(int rb, const Geo& g, int env)
 {
-    static const int env = [] {
-        const char* v = std::getenv("MGP_BRES_VN");
-        return v ? std::atoi(v) : -1;
-    }();
     int n = env < 0 ? 16 / (rb == 8 ? 8 : 4) : env;
     if (n != 0 && n != 1 && n != 2 && n != 4) n = 16 / (rb == 8 ? 8 : 4);
     while (n > 1 && g.hw % n) n >>= 1;
@@ -594,9 +590,10 @@ static void bres_v_t(void* u, const void* f, void* R, const Geo& g, const Geo& g
 }
 
 template <typename T, int D>
-static void bres_t(void* u, const void* f, void* R, const Geo& g, const Geo& gc, double h, double cl, hipStream_t s)
+static void bres_t(void* u, const void* f, void* R, const Geo& g, const Geo& gc, double h, double cl, int vn,
+                   hipStream_t s)
 {
-    const int n = bres_vn(sizeof(T), g);
+    const int n = bres_vn(sizeof(T), g, vn);
     if (n == 4 && sizeof(T) == 4) bres_v_t<T, D, 4>(u, f, R, g, gc, h, cl, s);
     else if (n >= 2) bres_v_t<T, D, 2>(u, f, R, g, gc, h, cl, s);
     else if (n == 1) bres_v_t<T, D, 1>(u, f, R, g, gc, h, cl, s);
@@ -604,15 +601,15 @@ static void bres_t(void* u, const void* f, void* R, const Geo& g, const Geo& gc,
 }
 
 hipError_t launch_black_residual_restrict(int rb, int dim, void* u, const void* f, void* R, Geo g, Geo gc, double h,
-                                          double cl, hipStream_t s)
+                                          double cl, const PieceTuning& pt, hipStream_t s)
 {
     if (!bres_supported(rb, g) || (dim == 3 && g.nz < 2)) return hipErrorInvalidValue;
     if (rb == 8) {
-        if (dim == 3) bres_t<double, 3>(u, f, R, g, gc, h, cl, s);
-        else bres_t<double, 2>(u, f, R, g, gc, h, cl, s);
+        if (dim == 3) bres_t<double, 3>(u, f, R, g, gc, h, cl, pt.bres_vn, s);
+        else bres_t<double, 2>(u, f, R, g, gc, h, cl, pt.bres_vn, s);
     } else {
-        if (dim == 3) bres_t<float, 3>(u, f, R, g, gc, h, cl, s);
-        else bres_t<float, 2>(u, f, R, g, gc, h, cl, s);
+        if (dim == 3) bres_t<float, 3>(u, f, R, g, gc, h, cl, pt.bres_vn, s);
+        else bres_t<float, 2>(u, f, R, g, gc, h, cl, pt.bres_vn, s);
     }
     return hipGetLastError();
 }
@@ -627,11 +624,11 @@ static void rbsweep_v_t(const void* src, const void* f, void* dst, const Geo& g,
 }
 
 template <typename T, int D>
-static void rbsweep_t(const void* src, const void* f, void* dst, Geo g, double h, double cl, bool store_red,
+static void rbsweep_t(const void* src, const void* f, void* dst, Geo g, double h, double cl, bool store_red, int vn,
                       hipStream_t s)
 {
     const Op<T, D> op = make_op<T, D>(h, cl);
-    const int n = bres_vn(sizeof(T), g);
+    const int n = bres_vn(sizeof(T), g, vn);
     if (n == 4 && sizeof(T) == 4) rbsweep_v_t<T, D, 4>(src, f, dst, g, op, store_red, s);
     else if (n >= 2) rbsweep_v_t<T, D, 2>(src, f, dst, g, op, store_red, s);
     else if (n == 1) rbsweep_v_t<T, D, 1>(src, f, dst, g, op, store_red, s);
@@ -642,15 +639,15 @@ static void rbsweep_t(const void* src, const void* f, void* dst, Geo g, double h
 }
 
 hipError_t launch_rb_sweep(int rb, int dim, const void* src, const void* f, void* dst, Geo g, double h, double cl,
-                           bool store_red, hipStream_t s)
+                           bool store_red, const PieceTuning& pt, hipStream_t s)
 {
     if (!bres_supported(rb, g) || (dim == 3 && g.nz < 2) || src == dst) return hipErrorInvalidValue;
     if (rb == 8) {
-        if (dim == 3) rbsweep_t<double, 3>(src, f, dst, g, h, cl, store_red, s);
-        else rbsweep_t<double, 2>(src, f, dst, g, h, cl, store_red, s);
+        if (dim == 3) rbsweep_t<double, 3>(src, f, dst, g, h, cl, store_red, pt.bres_vn, s);
+        else rbsweep_t<double, 2>(src, f, dst, g, h, cl, store_red, pt.bres_vn, s);
     } else {
-        if (dim == 3) rbsweep_t<float, 3>(src, f, dst, g, h, cl, store_red, s);
-        else rbsweep_t<float, 2>(src, f, dst, g, h, cl, store_red, s);
+        if (dim == 3) rbsweep_t<float, 3>(src, f, dst, g, h, cl, store_red, pt.bres_vn, s);
+        else rbsweep_t<float, 2>(src, f, dst, g, h, cl, store_red, pt.bres_vn, s);
     }
     return hipGetLastError();
 }

@@ -251,6 +251,15 @@ __device__ __forceinline__ int64_t pidx(const Geo& g, int i, int j, int64_t k)
     return k * g.P + c * g.H + (int64_t)j * g.hw + (i >> 1);
 }
 
+// The level-wide reductions (field stats, metrics, the err sum) walk a level's own slots, 2 H per plane, in one order
+// whatever the plane stride: slot c of those as an offset under the stride g.P.  With the stride padded
+// (MGP_PLANE_PAD) every thread then sums the values it sums unpadded, so the results keep their bits, and the pad
+// slots are not read.  lp = log2(2 H).
+__device__ __forceinline__ int64_t level_slot(int64_t c, int lp, int64_t P)
+{
+    return (c >> lp) * P + (c & (((int64_t)1 << lp) - 1));
+}
+
 // thread per packed slot: slot -> (k, c, j, m) -> i = 2m + (c ^ parity); i >= nx only when nx = 1.  A plane stride
 // beyond 2 H (MGP_PLANE_PAD) leaves pad slots after each plane's two halves: no cell (they stay 0)
 __device__ __forceinline__ bool slot_cell(int64_t s, const Geo& g, int& i, int& j, int64_t& k)

@@ -34,6 +34,20 @@ struct Geo {
     int64_t gnz;    // global planes of this level (1 in 2D)
 };
 
+// Kernel-form settings of the one-launch-per-piece cycle, read from the environment ONCE, when a context is created,
+// and kept in it (like FusedTuning below); a caller without a context passes the defaults.
+struct PieceTuning {
+    // MGP_RR_SCALAR_CELLS: residual + restriction below this many coarse cells runs one thread per coarse cell
+    // (k_resrestrict_s) instead of one 16-byte vector of them along x (k_resrestrict<T, D>)
+    int64_t rr_scalar_cells = (int64_t)1 << 22;
+    // MGP_RR_PAIR_CELLS: from this many coarse cells up to rr_scalar_cells, fp32 runs two coarse cells per thread
+    // (k_resrestrict<T, D, 2>); -1: the default rule, 2D from 2^18 and 3D never
+    int64_t rr_pair_cells = -1;
+    int bres_vn = -1;  // MGP_BRES_VN: cells per thread of k_bres / k_rbsweep (0 the scalar forms, 1 / 2 / 4; -1: 16 bytes)
+    bool nt = false;   // MGP_NT=1: the finest level's half-sweep stores non-temporally (k_half<T, D, 2, .>)
+};
+PieceTuning piece_tuning_from_env();
+
 // Launchers enqueue on `s` and return the launch's hipGetLastError().  rb = sizeof(real),
 // dim = 2 or 3.  `fine` selects the finest-level instantiation (a distinct symbol, so rocprofv3
 // reports the finest smoother on its own line).
@@ -70,7 +84,8 @@ hipError_t launch_sqdiff_field(int rb, const void* a, const void* b, void* out, 
 // gs: large levels use the grid-stride form (kGsBlocks workgroups, XCD-banded)
 int half_blocks(int rb, Geo g, bool gs);
 hipError_t launch_half_sweep(int rb, int dim, bool fine, int color, const void* other, const void* f, void* dst,
-                             const void* old, double* partials, Geo g, double h, double cl, bool gs, hipStream_t s);
+                             const void* old, double* partials, Geo g, double h, double cl, bool gs,
+                             const PieceTuning& pt, hipStream_t s);
 // The first red/black sweep of a fresh zero guess (cpu.lua:138) in one pass: u (both colours) from f
 // alone, bit-identical to the red and black half-sweeps reading u = 0.  Levels with hw >= 16 / rb.
 bool fresh_supported(int rb, const Geo& g);
@@ -86,19 +101,19 @@ hipError_t launch_post_first(int rb, int dim, int linear, void* u, const void* V
 // Fused residual + restriction (calcResidual + reduceResidual): R (coarse packed, pointing at the
 // coarse plane of this rank's fine plane 0; its Geo is gc) from u, f of the fine level.
 hipError_t launch_residual_restrict(int rb, int dim, const void* u, const void* f, void* R, Geo g, Geo gc, double h,
-                                    double cl, hipStream_t s);
+                                    double cl, const PieceTuning& pt, hipStream_t s);
 // The last black half-sweep of a red/black pre-smoothing + residual + restriction in one pass (k_bres): u's black
 // cells relaxed in place from its (final) red cells and f, R as launch_residual_restrict would compute it from the
 // swept u.  Bit-identical to launch_half_sweep(colour 1, in place) + launch_residual_restrict.  Real arithmetic
 // (rb 4 / 8), a replicated level (planes -1 and nz are not read) with nx, ny (and nz) >= 2.
 bool bres_supported(int rb, const Geo& g);
 hipError_t launch_black_residual_restrict(int rb, int dim, void* u, const void* f, void* R, Geo g, Geo gc, double h,
-                                          double cl, hipStream_t s);
+                                          double cl, const PieceTuning& pt, hipStream_t s);
 // One whole red/black sweep in one pass (k_rbsweep): dst's black cells (and with store_red its red ones) = the sweep
 // of src, read from src's black cells and f only (src != dst; same shapes as launch_black_residual_restrict).
 // Bit-identical to the red and black launch_half_sweep pair.
 hipError_t launch_rb_sweep(int rb, int dim, const void* src, const void* f, void* dst, Geo g, double h, double cl,
-                           bool store_red, hipStream_t s);
+                           bool store_red, const PieceTuning& pt, hipStream_t s);
 // Full-weighting restriction (mgp_opts.restriction, build-defined): r = f - A u of the level's own planes
 // into the scratch r (same packed layout and ghost planes as the level), then R (coarse packed, Geo gc)
 // from r, which must have current planes -1 and g.nz (zero at the physical boundary, the neighbours'
@@ -120,14 +135,16 @@ hipError_t launch_prolong_correct(int rb, int dim, int linear, void* u, const vo
                                   hipStream_t s, bool black_only = false);
 // Deterministic two-pass fp64 sum of (a - b)^2 over n elements into *out (ctr != nullptr: into
 // out[*ctr], then ++*ctr on the device).
+// lev (here and in launch_metrics): a and b are whole levels of that layout, n = lev->P * planes.  The sum then runs
+// over the level's own slots in the order of an unpadded plane stride, so MGP_PLANE_PAD does not change its bits.
 hipError_t launch_sqdiff_sum(int rb, const void* a, const void* b, int64_t n, double* partials, double* out,
-                             hipStream_t s, int* ctr = nullptr);
+                             hipStream_t s, int* ctr = nullptr, const Geo* lev = nullptr);
 // out[0..2] = {sum |1 - psi/psiOld| over nonzero entries, their count, sum (psi - psiOld)^2}
 // over n elements; partials needs 3 * kSumBlocks doubles.
 // Debugging check (cpu-raw.lua:126-140, gpu.lua:269-284): *first = min(*first, id) if p[0, n) holds a NaN or inf.
 hipError_t launch_nonfinite_check(int rb, const void* p, int64_t n, int id, int* first, hipStream_t s);
 hipError_t launch_metrics(int rb, const void* psi, const void* old, int64_t n, double* partials, double* out,
-                          hipStream_t s);
+                          hipStream_t s, const Geo* lev = nullptr);
 // out[0] = sum (f - A u)^2, out[1] = sum f^2 over the level's cells (fp64, wave-level then fixed-order
 // reductions).  partials: 2 * (resnorm_blocks() + sum_scratch(resnorm_blocks())) doubles.
 int resnorm_blocks(int rb, Geo g);

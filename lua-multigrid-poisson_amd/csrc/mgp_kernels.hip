@@ -109,14 +109,16 @@ __device__ __forceinline__ uint64_t real_bits(T v)
     }
 }
 
-template <typename T>
+// PAD: the plane stride is not 2 H (level_slot, mgp_device.h)
+template <typename T, bool PAD = false>
 __global__ __launch_bounds__(kBlock) void k_field_stats(const T* __restrict__ in, Geo g, uint64_t* __restrict__ hpart,
                                                         double* __restrict__ dpart)
 {
-    const int64_t n = g.P * g.nz;
+    const int64_t n = (PAD ? 2 * g.H : g.P) * g.nz;
     uint64_t h = 0;
     double s = 0.0, q = 0.0, mx = 0.0;
-    for (int64_t x = (int64_t)blockIdx.x * kBlock + threadIdx.x; x < n; x += (int64_t)gridDim.x * kBlock) {
+    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < n; c += (int64_t)gridDim.x * kBlock) {
+        const int64_t x = PAD ? level_slot(c, g.lhw + g.ly + 1, g.P) : c;
         int i, j;
         int64_t k;
         if (!slot_cell(x, g, i, j, k)) continue;
@@ -2460,12 +2462,15 @@ __global__ __launch_bounds__(kBlock) void k_copy16(const float4* __restrict__ sr
 // ---- reductions -----------------------------------------------------------------------------
 
 // ROUND: each square is first stored into the real-typed errorBuf (cpu-raw.lua:96-100, 249-253)
-template <typename T, bool ROUND = false>
+// PAD: n counts a level's own slots, planes of 2^lp of them at a stride of P (level_slot, mgp_device.h)
+template <typename T, bool ROUND = false, bool PAD = false>
 __global__ __launch_bounds__(kBlock) void k_sqdiff_partial(const T* __restrict__ a, const T* __restrict__ b,
-                                                           int64_t n, double* __restrict__ partials)
+                                                           int64_t n, double* __restrict__ partials, int lp = 0,
+                                                           int64_t P = 0)
 {
     double acc = 0.0;
-    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < n; c += (int64_t)gridDim.x * kBlock) {
+    for (int64_t x = (int64_t)blockIdx.x * kBlock + threadIdx.x; x < n; x += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = PAD ? level_slot(x, lp, P) : x;
         const double d = (double)a[c] - (double)b[c];
         acc += ROUND ? (double)(T)(d * d) : d * d;
     }
@@ -2475,12 +2480,14 @@ __global__ __launch_bounds__(kBlock) void k_sqdiff_partial(const T* __restrict__
 // calcRelErr + count + calcFrobErr of gpu.lua:173-200 / test-gpu-obj.lua:96-123, 216-247 in one
 // pass: per workgroup sum |1 - psi/psiOld| (in real, as errorBuf holds it), the number of nonzero
 // errorBuf entries and sum (psi - psiOld)^2, each into its own block of kSumBlocks partials.
-template <typename T>
+template <typename T, bool PAD = false>
 __global__ __launch_bounds__(kBlock) void k_metrics_partial(const T* __restrict__ psi, const T* __restrict__ old,
-                                                            int64_t n, double* __restrict__ partials)
+                                                            int64_t n, double* __restrict__ partials, int lp = 0,
+                                                            int64_t P = 0)
 {
     double rel = 0.0, cnt = 0.0, sq = 0.0;
-    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < n; c += (int64_t)gridDim.x * kBlock) {
+    for (int64_t x = (int64_t)blockIdx.x * kBlock + threadIdx.x; x < n; x += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = PAD ? level_slot(x, lp, P) : x;
         const T p = psi[c], o = old[c];
         const T e = (o != (T)0 && o != p) ? (T)fabs(1.0 - (double)(p / o)) : (T)0;
         if (e != (T)0) {
@@ -2674,7 +2681,8 @@ hipError_t launch_field_stats(int rb, const void* packed, Geo g, uint64_t* hpart
                               double* out_d, hipStream_t s)
 {
     const int nb = kSumBlocks;
-    MGP_REAL(rb, (k_field_stats<T><<<nb, kBlock, 0, s>>>((const T*)packed, g, hpart, dpart)));
+    if (g.P != 2 * g.H) MGP_REAL(rb, (k_field_stats<T, true><<<nb, kBlock, 0, s>>>((const T*)packed, g, hpart, dpart)));
+    else MGP_REAL(rb, (k_field_stats<T><<<nb, kBlock, 0, s>>>((const T*)packed, g, hpart, dpart)));
     k_field_stats_final<<<1, kBlock, 0, s>>>(hpart, dpart, nb, out_h, out_d);
     return hipGetLastError();
 }
@@ -2700,7 +2708,7 @@ int half_blocks(int rb, Geo g, bool gs)
 
 template <typename T, int D>
 static void half_t(bool fine, bool err, bool vec, bool gs, unsigned nb, int color, const void* other, const void* f, void* dst,
-                   const void* old, double* partials, Geo g, double h, double cl, hipStream_t s)
+                   const void* old, double* partials, Geo g, double h, double cl, bool nt, hipStream_t s)
 {
     const Op<T, D> op = make_op<T, D>(h, cl);
     const T* o_ = (const T*)other;
@@ -2717,10 +2725,6 @@ static void half_t(bool fine, bool err, bool vec, bool gs, unsigned nb, int colo
             else k_half_gs<T, D, 0, false><<<nb, kBlock, 0, s>>>(o_, f_, d_, w_, partials, g, color, op, items);
         }
     } else if (vec) {
-        static const bool nt = [] {
-            const char* v = std::getenv("MGP_NT");
-            return v && std::atoi(v) != 0;
-        }();
         if (fine && nt) {
             if (err) k_half<T, D, 2, true><<<nb, kBlock, 0, s>>>(o_, f_, d_, w_, partials, g, color, op);
             else k_half<T, D, 2, false><<<nb, kBlock, 0, s>>>(o_, f_, d_, w_, partials, g, color, op);
@@ -2748,8 +2752,19 @@ static void half_f32d(bool err, unsigned nb, int color, const void* other, const
     else k_half_s<float, D, false, double><<<nb, kBlock, 0, s>>>(o_, f_, (float*)dst, w_, partials, g, color, op);
 }
 
+PieceTuning piece_tuning_from_env()
+{
+    PieceTuning t;
+    if (const char* v = std::getenv("MGP_RR_SCALAR_CELLS")) t.rr_scalar_cells = std::atoll(v);
+    if (const char* v = std::getenv("MGP_RR_PAIR_CELLS")) t.rr_pair_cells = std::atoll(v);
+    if (const char* v = std::getenv("MGP_BRES_VN")) t.bres_vn = std::atoi(v);
+    if (const char* v = std::getenv("MGP_NT")) t.nt = std::atoi(v) != 0;
+    return t;
+}
+
 hipError_t launch_half_sweep(int rb, int dim, bool fine, int color, const void* other, const void* f, void* dst,
-                             const void* old, double* partials, Geo g, double h, double cl, bool gs, hipStream_t s)
+                             const void* old, double* partials, Geo g, double h, double cl, bool gs,
+                             const PieceTuning& pt, hipStream_t s)
 {
     const unsigned nb = (unsigned)half_blocks(rb, g, gs);
     if (rb == kRealF32D) {
@@ -2759,11 +2774,11 @@ hipError_t launch_half_sweep(int rb, int dim, bool fine, int color, const void* 
     }
     const bool err = old != nullptr, vec = half_vector(rb, g);
     if (rb == 8) {
-        if (dim == 3) half_t<double, 3>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, s);
-        else half_t<double, 2>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, s);
+        if (dim == 3) half_t<double, 3>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, pt.nt, s);
+        else half_t<double, 2>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, pt.nt, s);
     } else {
-        if (dim == 3) half_t<float, 3>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, s);
-        else half_t<float, 2>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, s);
+        if (dim == 3) half_t<float, 3>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, pt.nt, s);
+        else half_t<float, 2>(fine, err, vec, gs, nb, color, other, f, dst, old, partials, g, h, cl, pt.nt, s);
     }
     return hipGetLastError();
 }
@@ -2818,7 +2833,8 @@ hipError_t launch_fresh_sweep(int rb, int dim, const void* f, void* u, Geo g, do
 }
 
 template <typename T, int D>
-static void rr_t(const void* u, const void* f, void* R, Geo g, Geo gc, double h, double cl, hipStream_t s)
+static void rr_t(const void* u, const void* f, void* R, Geo g, Geo gc, double h, double cl, const PieceTuning& pt,
+                 hipStream_t s)
 {
     const Op<T, D> op = make_op<T, D>(h, cl);
     constexpr int n = VN<T>::n;
@@ -2826,16 +2842,10 @@ static void rr_t(const void* u, const void* f, void* R, Geo g, Geo gc, double h,
     const int64_t ncz = D == 3 ? g.nz / 2 : 1;
     // below 2^22 coarse cells one thread per coarse cell (more parallelism, shorter per-thread
     // chains) beats n cells along x: 256^3 -> 128^3 and below, 1.609 -> 1.570 ms per 512^3 cycle
-    static const int64_t scalar_below = [] {
-        const char* v = std::getenv("MGP_RR_SCALAR_CELLS");
-        return v ? std::atoll(v) : (int64_t)1 << 22;
-    }();
+    const int64_t scalar_below = pt.rr_scalar_cells;  // (MGP_RR_SCALAR_CELLS)
     // from MGP_RR_PAIR_CELLS coarse cells up to scalar_below: two coarse cells per thread (default: 2D from 2^18,
     // the 2048^2 level of configs[1]: cycle 0.2655 -> 0.2604 ms; 3D off, neutral at 512^3)
-    static const int64_t pair_env = [] {
-        const char* v = std::getenv("MGP_RR_PAIR_CELLS");
-        return v ? std::atoll(v) : (int64_t)-1;
-    }();
+    const int64_t pair_env = pt.rr_pair_cells;
     const int64_t pair_from = pair_env >= 0 ? pair_env : (D == 2 ? (int64_t)1 << 18 : INT64_MAX);
     const int64_t ccells = (int64_t)cx * (g.ny / 2) * ncz;
     if (cx >= n && ccells >= scalar_below) {
@@ -2851,7 +2861,7 @@ static void rr_t(const void* u, const void* f, void* R, Geo g, Geo gc, double h,
 }
 
 hipError_t launch_residual_restrict(int rb, int dim, const void* u, const void* f, void* R, Geo g, Geo gc, double h,
-                                    double cl, hipStream_t s)
+                                    double cl, const PieceTuning& pt, hipStream_t s)
 {
     if (rb == kRealF32D) {
         const int64_t items = (int64_t)(g.nx / 2) * (g.ny / 2) * (dim == 3 ? g.nz / 2 : 1);
@@ -2864,11 +2874,11 @@ hipError_t launch_residual_restrict(int rb, int dim, const void* u, const void* 
         return hipGetLastError();
     }
     if (rb == 8) {
-        if (dim == 3) rr_t<double, 3>(u, f, R, g, gc, h, cl, s);
-        else rr_t<double, 2>(u, f, R, g, gc, h, cl, s);
+        if (dim == 3) rr_t<double, 3>(u, f, R, g, gc, h, cl, pt, s);
+        else rr_t<double, 2>(u, f, R, g, gc, h, cl, pt, s);
     } else {
-        if (dim == 3) rr_t<float, 3>(u, f, R, g, gc, h, cl, s);
-        else rr_t<float, 2>(u, f, R, g, gc, h, cl, s);
+        if (dim == 3) rr_t<float, 3>(u, f, R, g, gc, h, cl, pt, s);
+        else rr_t<float, 2>(u, f, R, g, gc, h, cl, pt, s);
     }
     return hipGetLastError();
 }
@@ -3127,19 +3137,37 @@ hipError_t launch_copy16(int kind, const void* src, void* dst, int64_t bytes, hi
 }
 
 hipError_t launch_sqdiff_sum(int rb, const void* a, const void* b, int64_t n, double* partials, double* out,
-                             hipStream_t s, int* ctr)
+                             hipStream_t s, int* ctr, const Geo* lev)
 {
-    if (rb == kRealF32D)  // cpu-raw.lua's float errorBuf: each square rounded to float before the sum
-        k_sqdiff_partial<float, true><<<kSumBlocks, kBlock, 0, s>>>((const float*)a, (const float*)b, n, partials);
-    else MGP_REAL(rb, (k_sqdiff_partial<T><<<kSumBlocks, kBlock, 0, s>>>((const T*)a, (const T*)b, n, partials)));
+    const bool pad = lev && lev->P != 2 * lev->H;
+    const int lp = pad ? lev->lhw + lev->ly + 1 : 0;
+    const int64_t P = pad ? lev->P : 0;
+    if (pad) n = n / P * 2 * lev->H;
+    if (rb == kRealF32D) {  // cpu-raw.lua's float errorBuf: each square rounded to float before the sum
+        if (pad)
+            k_sqdiff_partial<float, true, true><<<kSumBlocks, kBlock, 0, s>>>((const float*)a, (const float*)b, n,
+                                                                              partials, lp, P);
+        else k_sqdiff_partial<float, true><<<kSumBlocks, kBlock, 0, s>>>((const float*)a, (const float*)b, n, partials);
+    } else if (pad) {
+        MGP_REAL(rb, (k_sqdiff_partial<T, false, true><<<kSumBlocks, kBlock, 0, s>>>((const T*)a, (const T*)b, n,
+                                                                                    partials, lp, P)));
+    } else {
+        MGP_REAL(rb, (k_sqdiff_partial<T><<<kSumBlocks, kBlock, 0, s>>>((const T*)a, (const T*)b, n, partials)));
+    }
     k_sum_n<<<1, 1024, 0, s>>>(partials, kSumBlocks, out, ctr);
     return hipGetLastError();
 }
 
 hipError_t launch_metrics(int rb, const void* psi, const void* old, int64_t n, double* partials, double* out,
-                          hipStream_t s)
+                          hipStream_t s, const Geo* lev)
 {
-    MGP_REAL(rb, (k_metrics_partial<T><<<kSumBlocks, kBlock, 0, s>>>((const T*)psi, (const T*)old, n, partials)));
+    if (lev && lev->P != 2 * lev->H) {
+        const int64_t nl = n / lev->P * 2 * lev->H;
+        MGP_REAL(rb, (k_metrics_partial<T, true><<<kSumBlocks, kBlock, 0, s>>>((const T*)psi, (const T*)old, nl, partials,
+                                                                              lev->lhw + lev->ly + 1, lev->P)));
+    } else {
+        MGP_REAL(rb, (k_metrics_partial<T><<<kSumBlocks, kBlock, 0, s>>>((const T*)psi, (const T*)old, n, partials)));
+    }
     for (int q = 0; q < 3; ++q) k_sum_n<<<1, 1024, 0, s>>>(partials + q * kSumBlocks, kSumBlocks, out + q);
     return hipGetLastError();
 }

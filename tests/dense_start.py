@@ -1,4 +1,4 @@
-"""Dense random level-0 start states for whole-cycle parity (test_gpu_dense.py, test_gpu_dense_fw.py) and their CPU guard
+"""Dense random level-0 start states for whole-cycle parity (test_gpu_dense.py, test_gpu_dense_fw.py, test_gpu_switches.py) and their CPU guard
 (test_dense_inputs.py) — TEST INFRASTRUCTURE ONLY.
 
 init_point_charge() leaves one non-zero cell in f and in psi and zeros everywhere else, so a cycle started from it
@@ -143,6 +143,21 @@ CASES = {
     "raw-32-fw": (dict(dim=3, n=(32, 32, 32), **RAW, **RB, **LC, **FW), 1141),
     "raw-16x32x16-F-warm": (dict(dim=3, n=(16, 32, 16), smoother="jacobi", nu1=3, nu2=2, cycle="F",
                                  coarse_init="warm", **RAW, **LC), 1161),
+    # ---- test_gpu_switches.py ----
+    # 12. the tile-patch order of the fused phases: launches of 1024 workgroups (fp32 512 x 512 x 128 and fp64 256^3
+    # in 16-plane chunks), the fp32 box with the full weighting fused into PRE as well; the one-tile fp64 box gives
+    # the threads per workgroup of the fp64 kernels
+    "patch-512x512x128-f32": (dict(dim=3, n=(512, 512, 128), real="float", **RB, **LC), 1201),
+    "patch-256-f64": (dict(dim=3, n=(256, 256, 256), real="double", **RB, **LC), 1221),
+    "patch-fw-512x512x128-f32": (dict(dim=3, n=(512, 512, 128), real="float", **RB, **LC, **FW), 1241),
+    "zs-f64-64x32x16": (dict(dim=3, n=(64, 32, 16), real="double", **RB, **LC), 1381),
+    # 13. MGP_PLANE_PAD: level 0's planes hold exactly 2^16 slots, the smallest that takes the padded stride
+    "pad-256x256x16-f32": (dict(dim=3, n=(256, 256, 16), real="float", **RB, **LC), 1261),
+    "pad-256x256x16-f64": (dict(dim=3, n=(256, 256, 16), real="double", **RB, **LC), 1281),
+    "pad-256x256x16-f64-jacobi": (dict(dim=3, n=(256, 256, 16), real="double", smoother="jacobi", nu1=2, nu2=2, **LC), 1301),
+    "pad-256x256x16-f32-fw": (dict(dim=3, n=(256, 256, 16), real="float", **RB, **LC, **FW), 1321),
+    "pad-256x256x16-f64-gslex": (dict(dim=3, n=(256, 256, 16), real="double", smoother="gs_lex", nu1=2, nu2=2), 1341),
+    "pad-slab-256x256x32-f32": (dict(dim=3, n=(256, 256, 32), real="float", **RB, **LC), 1361),
 }
 RESET_SEED_OFFSET = 10  # the second pair of fields of the cases in SECOND_FIELDS: seed + 10 (psi), seed + 11 (f)
 # the cases that set level 0 again in mid-run

@@ -32,7 +32,12 @@ SPLIT_NAME = "k_zs_split<float, false>"
 # every switch a case may set; a variant's environment is these cleared, then its own
 SWITCHES = ("MGP_FUSED", "MGP_FUSED_MIN_CELLS", "MGP_ZPOST_MIN_CELLS", "MGP_ZS_SPLIT", "MGP_ZS_WIDE", "MGP_LAZY_ZERO",
             "MGP_YS_MIN_CELLS", "MGP_YS_HALF", "MGP_BLK", "MGP_BLK2", "MGP_BRES", "MGP_TAIL", "MGP_TAIL_CUBIC",
-            "MGP_FRESH", "MGP_GRAPH", "MGP_RESFW", "MGP_ZS_FWF")
+            "MGP_FRESH", "MGP_GRAPH", "MGP_RESFW", "MGP_ZS_FWF",
+            # test_gpu_switches.py's
+            "MGP_ZS_WGS", "MGP_ZS_PATCH", "MGP_ZS_PATCH_PRE", "MGP_ZS_PATCH_POST", "MGP_ZS_SPLIT_POST",
+            "MGP_ZS_SPLIT_POST_MIN_CELLS", "MGP_ZS_POST_ZC", "MGP_PLANE_PAD", "MGP_LAZY_ZERO_FUSED", "MGP_ERRS_HOST",
+            "MGP_PRECAPTURE", "MGP_TAIL_CELLS", "MGP_BLK_CELLS", "MGP_BRES_VN", "MGP_RR_SCALAR_CELLS",
+            "MGP_RR_PAIR_CELLS", "MGP_NT")
 
 
 def _mg():

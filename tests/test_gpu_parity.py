@@ -193,7 +193,10 @@ def test_cycles_box_match_oracle(box):
 @pytest.mark.parametrize("real", ["double", "float"])
 @pytest.mark.parametrize("bc", ["zero", "consistent"])
 def test_residual_restrict_tiled3d(box, real, bc):
-    """The LDS-tiled 3D residual+restriction kernel (nx % 64 == 0, ny % 16 == 0) vs the oracle."""
+    """mgp_residual_restrict on 3D levels 0 and 1 vs the oracle.  Every level here has fewer than 2^22 coarse cells
+    (the largest, 256 x 256 x 32, has 2^18), so this runs the scalar form k_resrestrict_s (one thread per coarse
+    cell); the pair and vector forms are test_gpu_switches.py's.  (The name is from an LDS-tiled kernel that no
+    longer exists.)"""
     ctx = _ctx(dim=3, n=box, real=real, coarse_bc=bc)
     for level in (0, 1):
         shp = ctx.shape(level)
