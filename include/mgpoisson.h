@@ -165,7 +165,9 @@ int         mgp_cycles(mgp_ctx* c, int32_t k, double* errs);
 
 /* MultigridCPURaw:twoGrid(h, u, f, L) (cpu-raw.lua:186; gpu.lua:296): one cycle from the level of
  * size L with spacing h on caller buffers of L^dim reals (mem = MGP_MEM_HOST | MGP_MEM_DEVICE);
- * u is updated in place, f is read only.  Single-GPU contexts only. */
+ * u is updated in place, f is read only.  The level's own u / f (on the finest size the solver's psi and f) and
+ * psiOld of the last outer iteration (mgp_metrics, MGP_FIELD_PSI_OLD / _ERROR) are unchanged on every engine; the
+ * levels below are the cycle's scratch (rs, Rs, vs, Vs) and do change.  Single-GPU contexts only. */
 int         mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int mem);
 
 /* Level-granular pieces of twoGrid (cpu-raw.lua:198-236), for hybrid hand-off (cpu-gpu.lua:17-52)
@@ -227,8 +229,10 @@ int         mgp_cg_solve(mgp_ctx* c, double epsilon, int32_t maxiter, void* x_ou
  * current u / f.  MGP_ERR_ARG for real_bytes = 8 or MGP_ARITH_DOUBLE; MGP_ERR_STATE for world > 1, a loopback
  * context, a group's rank context, MGP_TRANSPORT=rccl, or when already active; MGP_ERR_OOM leaves the context as it
  * was.  While active, level 0's fp32 f / u are the scratch of the inner solve (mgp_get_field returns the last
- * narrowed defect / the last correction e); mgp_cycle, mgp_cycles, mgp_two_grid, mgp_metrics, mgp_cg_solve and
- * level-0 mgp_set_field / mgp_set_planes return MGP_ERR_STATE; mgp_init_point_charge also sets the fp64 fields.
+ * narrowed defect / the last correction e); mgp_cycle, mgp_cycles, mgp_two_grid, mgp_metrics, mgp_cg_solve,
+ * level-0 mgp_set_field / mgp_set_planes and reads of MGP_FIELD_PSI_OLD / _ERROR (the outer iteration is the fp64
+ * one, whose psiOld is not stored; after mgp_refine_end they need a new outer iteration) return MGP_ERR_STATE;
+ * mgp_init_point_charge also sets the fp64 fields.
  * mgp_refine_end stores the round-to-nearest narrowing of psi / f into level 0's u / f and frees the fp64 fields
  * (mgp_destroy frees them as well): an ordinary fp32 context again.  Every mgp_refine_* call but begin returns
  * MGP_ERR_STATE while refinement is not active. */

@@ -2535,7 +2535,8 @@ static int field_source(mgp_ctx* c, int level, int which, char** src, char** scr
         return MGP_OK;
     case MGP_FIELD_PSI_OLD:
     case MGP_FIELD_ERROR:
-        if (level != 0 || !c->metrics_old)
+        // (while refining the outer iteration is the fp64 one, whose psiOld is not stored: the inner cycles' is none)
+        if (level != 0 || !c->metrics_old || c->refining())
             return c->fail(MGP_ERR_STATE, "psiOld / errorBuf: level 0 only, after an outer iteration with err_mode 1 "
                                           "that kept psiOld (not with MGP_KEEP_PSI_OLD=0 on the temporally blocked finest level)");
         break;
@@ -2775,6 +2776,25 @@ int mgp_cycle(mgp_ctx* c, double* err_out)
     return rc;
 }
 
+// psiOld outside the outer loop.  With the fused err the last outer iteration's psiOld is level 0's t buffer
+// (update_metrics_old), which the out-of-place phases of a cycle from level 0 write: the temporally blocked PRE and
+// POST, k_blk.  The reference sets psiOld in the outer loop only (cpu.lua:200; twoGrid never touches it), so a cycle
+// from level 0 outside the outer loop (mgp_two_grid) first moves psiOld into the snapshot buffer (unused on this
+// path otherwise, allocated on first need); the next outer iteration points metrics_old at t again.
+static int keep_psi_old(mgp_ctx* c)
+{
+    if (!c->metrics_old || !c->err_fuse || c->metrics_old == c->psi_old) return MGP_OK;
+    const Level& L0 = c->lev[0];
+    const size_t bytes = (size_t)(L0.g.P * L0.g.nz) * c->rb;
+    if (!c->psi_old && hipMalloc(&c->psi_old, bytes) != hipSuccess) {
+        c->psi_old = nullptr;
+        return c->fail(MGP_ERR_OOM, "no room to keep psiOld of the last outer iteration");
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->psi_old, c->metrics_old, bytes, hipMemcpyDeviceToDevice, c->s));
+    c->metrics_old = c->psi_old;
+    return MGP_OK;
+}
+
 int mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int mem)
 {
     if (!c || !u || !f) return MGP_ERR_ARG;
@@ -2789,6 +2809,7 @@ int mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int me
         const int64_t n = level_count(Lv);
         const size_t bytes = (size_t)Lv.alloc * c->rb;
         TRY(materialize_zero(c, Lv));
+        if (l == 0) TRY(keep_psi_old(c));  // twoGrid never touches psiOld (cpu-raw.lua:186-236)
         char *su = nullptr, *sf = nullptr;
         if (hipMalloc(&su, bytes) != hipSuccess || hipMalloc(&sf, bytes) != hipSuccess) {
             if (su) (void)hipFree(su);
@@ -2813,7 +2834,7 @@ int mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int me
                          c->dbg_names[(size_t)dbg_first].c_str());
         if (c->debug) c->dbg_names.clear();
         step(mgp_get_field(c, l, MGP_FIELD_U, u, n, mem));
-        TRY(materialize_zero(c, Lv));
+        step(materialize_zero(c, Lv));  // (no early return: su / sf are freed below)
         const bool r1 = hipMemcpyAsync(Lv.u, su, bytes, hipMemcpyDeviceToDevice, c->s) == hipSuccess;
         const bool r2 = hipMemcpyAsync(Lv.f, sf, bytes, hipMemcpyDeviceToDevice, c->s) == hipSuccess;
         const bool r3 = hipStreamSynchronize(c->s) == hipSuccess;
