@@ -45,7 +45,19 @@ enum { MGP_JACOBI = 0, MGP_RBGS = 1, MGP_GS_LEX = 2 };
 enum { MGP_CYCLE_V = 0, MGP_CYCLE_F = 1 };             /* twoGrid recursion (gamma 1) / F-cycle */
 enum { MGP_PROLONG_PC = 0, MGP_PROLONG_LINEAR = 1 };   /* cpu.lua:142-150 injection / (tri)linear */
 enum { MGP_COARSE_FRESH = 0, MGP_COARSE_WARM = 1 };    /* cpu.lua:138 zeros / cpu-raw.lua:221 Vs */
-enum { MGP_BC_ZERO = 0, MGP_BC_CONSISTENT = 1 };       /* coarse ghost: 0 (ref) / extrapolated */
+/* Box boundary, through the per-level coefficient c_l of ghost = -c_l * (boundary cell):
+ *   MGP_BC_ZERO        the ghost cell CENTRE is 0 on every level (the reference, cpu.lua:28-33): c_l = 0
+ *   MGP_BC_CONSISTENT  the same on level 0; the coarse levels' zero moved to that place: c_l = (2^l - 1) / (2^l + 1)
+ *   MGP_BC_FACE        u = 0 ON the box face (build-defined): ghost = -u, c_l = +1 on every level, level 0 included
+ *   MGP_BC_NEUMANN     du/dn = 0 on the box face (build-defined; the ghost the reference carries commented out as
+ *                      `--u[i][j]` on every stencil line, cpu.lua:28-31, 45-48, 114-117, and its "periodic? neumann"
+ *                      branch of the one-cell solve, cpu.lua:79-86): ghost = +u, c_l = -1 on every level.  psi is
+ *                      determined up to a constant and f must sum to 0 (remove its mean first).  The one-cell level's
+ *                      diagonal is 0: a cell whose diagonal is 0 is relaxed to +0 whatever f holds (the minimum-norm
+ *                      choice).  The cycle itself does not project.
+ * The diagonal of a cell with nb faces on the box is (-2 dim - nb c_l) / h^2, the linear prolongation reads an
+ * out-of-box coarse value as -c_l * (boundary value) per axis, the full weighting's face weight is 3 - c_l. */
+enum { MGP_BC_ZERO = 0, MGP_BC_CONSISTENT = 1, MGP_BC_FACE = 2, MGP_BC_NEUMANN = 3 };
 /* restriction: the 2^dim cell average of cpu.lua:127-135 (reduceResidual) or the cell-centred full
  * weighting (north_star "full-weighting restriction"): the adjoint of the linear prolongation, per axis
  * (1, 3, 3, 1) / 8 over fine cells 2I-1 .. 2I+2, face weight (3 - c) next to the box boundary */
@@ -85,7 +97,7 @@ typedef struct mgp_opts {
     int32_t cycle;         /* MGP_CYCLE_V | MGP_CYCLE_F */
     int32_t prolong;       /* MGP_PROLONG_PC | MGP_PROLONG_LINEAR */
     int32_t coarse_init;   /* MGP_COARSE_FRESH | MGP_COARSE_WARM */
-    int32_t coarse_bc;     /* MGP_BC_ZERO | MGP_BC_CONSISTENT */
+    int32_t coarse_bc;     /* MGP_BC_ZERO | _CONSISTENT | _FACE | _NEUMANN */
     int32_t coarse_sweeps; /* sweeps on a coarsest level with more than one cell */
     int32_t err_mode;      /* 1: psiOld snapshot + RMS update per cycle (cpu.lua:200-203); 0: off */
     int32_t device;        /* HIP device ordinal; -1 = current device */
@@ -205,9 +217,22 @@ int         mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* fro
  * converged relative residual ||r|| / ||f||. */
 int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm);
 
+/* Removing a field's mean (build-defined; a plain field operation under every boundary).  MGP_BC_NEUMANN determines
+ * psi up to a constant and needs sum f = 0: remove f's mean before the first cycle and psi's after the last one (the
+ * cycle itself does not project, so err, psiOld and graph replay are those of the other boundaries).  which =
+ * MGP_FIELD_U | MGP_FIELD_F of any level.  S = the fp64 sum of the field's cells in a fixed order (per wave, per
+ * workgroup, then fixed; all-reduced over the ranks on a distributed level: mgp_field_stats' and mgp_residual_norm's
+ * scheme), m = S / N in double over the level's N global cells, every cell becomes RN((double)x - m), *mean = m
+ * (mean may be NULL).  One reduction pass and one 16-byte streaming pass on the packed layout; pad cells and ghost
+ * planes do not enter the sum.  Afterwards the field counts as written (its ghost planes are exchanged again on a
+ * slab level), and on level 0 psiOld and the metrics are invalid until the next outer iteration (mgp_metrics,
+ * MGP_FIELD_PSI_OLD / _ERROR: MGP_ERR_STATE).  While refinement is active level 0 is refused (MGP_ERR_STATE): use
+ * mgp_refine_remove_mean. */
+int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
+
 /* The reference's Krylov cross-check (test/converge-multigrid-vs-krylov.lua:38-69, solver.conjgrad) on
  * the device, as an independent second oracle for the converged multigrid answer: matrix-free
- * conjugate gradients on the finest level's operator (same 5-/7-point stencil, ghost 0) from
+ * conjugate gradients on the finest level's operator (same 5-/7-point stencil and box boundary) from
  * x0 = -f with b = f, fp64 dot products, stopping when rSq / bSq < epsilon or after maxiter
  * iterations.  The solution goes to x_out (level-0 cells, x fastest; may be NULL); linf_hist (maxiter
  * doubles, may be NULL) gets |x|_inf after every iteration, the quantity the reference plots.  The
@@ -243,6 +268,8 @@ int         mgp_refine_end(mgp_ctx* c);
  * host or device memory, through the bounded staging buffer. */
 int         mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int mem);
 int         mgp_refine_get(const mgp_ctx* c, int which, double* dst, int64_t count, int mem);
+/* mgp_remove_mean of the fp64 psi (MGP_REFINE_PSI) or f (MGP_REFINE_F). */
+int         mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean);
 /* *rnorm = ||f - A psi||_2, *fnorm = ||f||_2 of the fp64 fields (fp64 sums: per wave, per workgroup, fixed order);
  * psi is not changed (level 0's fp32 f receives the narrowed defect). */
 int         mgp_refine_residual(mgp_ctx* c, double* rnorm, double* fnorm);
@@ -289,6 +316,7 @@ int         mgp_group_set_field(mgp_group* g, int level, int which, const void* 
 int         mgp_group_get_field(mgp_group* g, int level, int which, void* dst, int64_t count, int mem);
 int         mgp_group_residual_norm(mgp_group* g, int level, double* rnorm, double* fnorm);
 int         mgp_group_field_stats(mgp_group* g, int level, int which, uint64_t* hash, double stats[3]);
+int         mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean);   /* mgp_remove_mean on every rank */
 
 /* Batched solves (build-defined; the reference solves one box): B independent members of ONE shape in one
  * hierarchy on one GPU.  Every kernel of a cycle covers all members in one launch (the launches per cycle do not
@@ -298,7 +326,7 @@ int         mgp_group_field_stats(mgp_group* g, int level, int which, uint64_t* 
  * per piece (engine 0).  A batch owns one stream and replays ONE captured cycle (MGP_GRAPH=0: eager launches,
  * identical results); it is not thread-safe.
  * Options (`o` describes one member): dim 2 / 3, power-of-two axes, real_bytes 4 / 8 with MGP_ARITH_REAL, MGP_JACOBI
- * or MGP_RBGS, V / F, both prolongations, fresh / warm, both coarse boundaries, coarse_sweeps, err_mode 0 / 1.
+ * or MGP_RBGS, V / F, both prolongations, fresh / warm, every coarse_bc, coarse_sweeps, err_mode 0 / 1.
  * MGP_ERR_ARG naming the field, before any device call: batch < 1, world != 1, MGP_GS_LEX, MGP_ARITH_DOUBLE,
  * MGP_RESTRICT_FULL_WEIGHTING, a member (n) of more than 2^24 level-0 cells (one such box fills the GPU: use
  * mgp_create), batch * cells >= 2^31.  MGP_ERR_OOM leaves nothing allocated.
@@ -333,6 +361,9 @@ int         mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32
 /* Per member mgp_residual_norm of level 0: rnorm[m] = ||f - A u||_2, fnorm[m] = ||f||_2 (fp64 sums: per wave,
  * per workgroup, then in a fixed order); either may be NULL. */
 int         mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm);
+/* mgp_remove_mean per member (stopped members included): means[B] (may be NULL); each member's sum per wave, then
+ * per workgroup in a fixed order. */
+int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
 /* Kernel launches (graph nodes included) one cycle of the last mgp_batch_cycles / mgp_batch_solve enqueued. */
 int         mgp_batch_launches(const mgp_batch* b, int64_t* per_cycle);
 

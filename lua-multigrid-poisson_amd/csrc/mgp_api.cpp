@@ -33,6 +33,7 @@
 #include "../../include/mgpoisson.h"
 
 using mgp::Geo;
+using mgp::coarse_coef;
 
 namespace {
 
@@ -109,7 +110,7 @@ int plan_levels(const mgp_opts& o, std::vector<LevelPlan>& out, std::string& err
     if (o.cycle != MGP_CYCLE_V && o.cycle != MGP_CYCLE_F) { err = "unknown cycle"; return MGP_ERR_ARG; }
     if (o.prolong != MGP_PROLONG_PC && o.prolong != MGP_PROLONG_LINEAR) { err = "unknown prolong"; return MGP_ERR_ARG; }
     if (o.coarse_init != MGP_COARSE_FRESH && o.coarse_init != MGP_COARSE_WARM) { err = "unknown coarse_init"; return MGP_ERR_ARG; }
-    if (o.coarse_bc != MGP_BC_ZERO && o.coarse_bc != MGP_BC_CONSISTENT) { err = "unknown coarse_bc"; return MGP_ERR_ARG; }
+    if (o.coarse_bc < MGP_BC_ZERO || o.coarse_bc > MGP_BC_NEUMANN) { err = "unknown coarse_bc"; return MGP_ERR_ARG; }
     if (o.restriction != MGP_RESTRICT_AVERAGE && o.restriction != MGP_RESTRICT_FULL_WEIGHTING) {
         err = "unknown restriction";
         return MGP_ERR_ARG;
@@ -145,13 +146,6 @@ int plan_levels(const mgp_opts& o, std::vector<LevelPlan>& out, std::string& err
 int real_kind(const mgp_opts& o)
 {
     return o.real_bytes == 4 && o.arith == MGP_ARITH_DOUBLE ? mgp::kRealF32D : o.real_bytes;
-}
-
-double coarse_coef(int coarse_bc, int level)
-{
-    if (coarse_bc != MGP_BC_CONSISTENT || level <= 0) return 0.0;
-    double p = std::ldexp(1.0, level);
-    return (p - 1.0) / (p + 1.0);
 }
 
 }  // namespace
@@ -263,6 +257,7 @@ struct mgp_ctx {
     double* d_metrics = nullptr;  // 3 * kSumBlocks partials + 3 results
     double* d_rn = nullptr;       // residual-norm partials (+ 2 results), d_rn_cap doubles
     int64_t d_rn_cap = 0;
+    double* d_mean = nullptr;     // mgp_remove_mean: kSumBlocks partials + {sum, mean}
     char* psi_old = nullptr;  // snapshot buffer (Jacobi path)
     // full-weighting restriction: the residual of the level being restricted (level-0 sized, with ghost planes)
     char* rscratch = nullptr;
@@ -2155,6 +2150,7 @@ static void destroy_impl(mgp_ctx* c)
     if (c->lb_red) (void)hipFree(c->lb_red);
     if (c->d_metrics) (void)hipFree(c->d_metrics);
     if (c->d_rn) (void)hipFree(c->d_rn);
+    if (c->d_mean) (void)hipFree(c->d_mean);
     if (c->d_dbg) (void)hipFree(c->d_dbg);
     for (auto& m : c->marks)
         if (m.ev) (void)hipEventDestroy(m.ev);
@@ -2996,6 +2992,50 @@ int mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm)
     return MGP_OK;
 }
 
+// The two passes of mgp_remove_mean / mgp_refine_remove_mean on one packed field of level L's layout (rb = 4 / 8):
+// the fixed-order fp64 sum (all-reduced on a distributed level), m = S / N, every cell RN((double)x - m)
+static int remove_mean_passes(mgp_ctx* c, Level& L, void* field, int rb, double* mean)
+{
+    if (!c->d_mean) {
+        HIP_TRY(c, hipMalloc(&c->d_mean, sizeof(double) * (mgp::kSumBlocks + 2)));
+    }
+    double* out = c->d_mean + mgp::kSumBlocks;
+    HIP_TRY(c, mgp::launch_mean_sum(rb, field, L.g, c->d_mean, out, c->s));
+    WaitScope w(c);  // the all-reduce and the read-back after it wait for the peers
+    if (L.p.dist) {
+        if (c->lb)
+            TRY(lb_allreduce(c, out, 1));
+        else
+            NCCL_CALL(c, c->comm, ncclAllReduce(out, out, 1, ncclDouble, ncclSum, c->comm, c->s), "mean all-reduce");
+    }
+    const double cells = (double)(L.p.nx * L.p.ny * L.p.gnz);
+    HIP_TRY(c, mgp::launch_mean_sub(rb, field, L.g, cells, out, c->s));
+    double m = 0.0;
+    HIP_TRY(c, hipMemcpyAsync(&m, out + 1, sizeof m, hipMemcpyDeviceToHost, c->s));
+    TRY(sync_and_check(c));
+    if (mean) *mean = m;
+    return MGP_OK;
+}
+
+int mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (check_level(c, level) != MGP_OK || (which != MGP_FIELD_U && which != MGP_FIELD_F))
+        return c->fail(MGP_ERR_ARG, "mgp_remove_mean: bad level / field (MGP_FIELD_U or MGP_FIELD_F)");
+    if (level == 0 && c->refining()) return refine_refuses(c, "mgp_remove_mean(level 0)");
+    Level& L = c->lev[level];
+    if (which == MGP_FIELD_U) TRY(materialize_zero(c, L));
+    TRY(remove_mean_passes(c, L, c->ui(L, which == MGP_FIELD_U ? L.u : L.f), c->rb, mean));
+    if (which == MGP_FIELD_U) {  // the field was written: its ghost planes are stale on a slab level
+        L.ghost_ok = !L.p.dist;
+        L.ghost_zero = false;
+    } else {
+        L.fghost_ok = !L.p.dist;
+    }
+    if (level == 0) c->metrics_old = nullptr;  // psiOld and the metrics describe an iterate that is gone
+    return MGP_OK;
+}
+
 // ---- mixed-precision defect correction (cpu.lua:196-216 with real = 'double', around the fp32 cycles) ----
 
 static int refine_active(mgp_ctx* c, const char* what)
@@ -3122,6 +3162,15 @@ int mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int 
     return refine_io(c, which, const_cast<double*>(src), count, mem, true, "mgp_refine_set");
 }
 
+int mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(refine_active(c, "mgp_refine_remove_mean"));
+    if (which != MGP_REFINE_PSI && which != MGP_REFINE_F)
+        return c->fail(MGP_ERR_ARG, "mgp_refine_remove_mean: which must be MGP_REFINE_PSI or MGP_REFINE_F");
+    return remove_mean_passes(c, c->lev[0], ui64(c, which == MGP_REFINE_PSI ? c->psi64 : c->f64), 8, mean);
+}
+
 int mgp_refine_get(const mgp_ctx* cc, int which, double* dst, int64_t count, int mem)
 {
     mgp_ctx* c = const_cast<mgp_ctx*>(cc);
@@ -3139,7 +3188,8 @@ static int refine_defect(mgp_ctx* c, bool zero)
     hipEvent_t e;
     TRY(timed_begin_on(c, c->s, &e));
     HIP_TRY(c, mgp::launch_defect(c->o.dim, ui64(c, c->psi64), ui64(c, c->f64), (float*)c->ui(L, L.f),
-                                  zero ? (float*)c->ui(L, L.u) : nullptr, L.g, level_h(c, 0), c->d_ref, out, c->s));
+                                  zero ? (float*)c->ui(L, L.u) : nullptr, L.g, level_h(c, 0),
+                                  coarse_coef(c->o.coarse_bc, 0), c->d_ref, out, c->s));
     TRY(timed_end_on(c, c->s, e, MGP_TIMING_REFINE_DEFECT, (zero ? 24.0 : 20.0) * cells));
     fields_written(c);
     c->metrics_old = nullptr;
@@ -3261,7 +3311,7 @@ int mgp_cg_solve(mgp_ctx* c, double epsilon, int32_t maxiter, void* x_out, int m
     mgp::CgArgs a{};
     a.g = L.g;
     a.h = level_h(c, 0);
-    a.cl = 0.0;
+    a.cl = coarse_coef(c->o.coarse_bc, 0);  // (level 0's boundary: 0 but under MGP_BC_FACE / _NEUMANN)
     a.x = c->ui(L, buf[0]);
     a.r = c->ui(L, buf[1]);
     a.p = c->ui(L, buf[2]);
@@ -3732,6 +3782,15 @@ int mgp_group_residual_norm(mgp_group* g, int level, double* rnorm, double* fnor
     TRY(group_run(g, [&](mgp_ctx* c, int r) { return mgp_residual_norm(c, level, &rn[(size_t)r], &fn[(size_t)r]); }));
     if (rnorm) *rnorm = rn[0];  // all-reduced: every rank holds the global norms
     if (fnorm) *fnorm = fn[0];
+    return MGP_OK;
+}
+
+int mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean)
+{
+    if (!g) return MGP_ERR_ARG;
+    std::vector<double> m(g->ranks.size());
+    TRY(group_run(g, [&](mgp_ctx* c, int r) { return mgp_remove_mean(c, level, which, &m[(size_t)r]); }));
+    if (mean) *mean = m[0];  // (the sum is all-reduced on a distributed level, a replicated level is the same on every rank)
     return MGP_OK;
 }
 

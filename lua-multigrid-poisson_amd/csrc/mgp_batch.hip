@@ -119,7 +119,7 @@ __device__ __forceinline__ void sweep_part(const T* src, const T* f, T* dst, con
         if (!slot_of(s, g, i, j, k)) continue;
         int nb;
         const T sum = nbsum<T, DIM>(src, g, s, i, j, k, nb);
-        dst[s] = L.op.relax(sum, f[s], nb);
+        dst[s] = L.op.relax_z(sum, f[s], nb);
     }
 }
 
@@ -243,6 +243,40 @@ __global__ __launch_bounds__(kBlock) void k_batch_err(const T* u, const T* old, 
         acc[0] += d * d;
     }
     block_sums<1>(acc, partials + blockIdx.x, 0);
+}
+
+// mgp_batch_remove_mean, one workgroup per member: out[m] = the fp64 sum of the member's cells (per thread, per wave,
+// the waves in order), out[B + m] = that sum / cells
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_batch_mean_sum(const T* __restrict__ x, Geo lg, int64_t slots, double cells,
+                                                           int B, double* __restrict__ out)
+{
+    const int m = (int)blockIdx.x;
+    const MGeo g = mgeo(lg);
+    const T* const xm = x + (int64_t)m * slots;
+    double acc[1] = {0.0};
+    for (int s = (int)threadIdx.x; s < g.nz * g.P; s += kBlock) {
+        int i, j, k;
+        if (slot_of(s, g, i, j, k)) acc[0] += (double)xm[s];
+    }
+    block_sums<1>(acc, out + m, 0);
+    if (threadIdx.x == 0) out[B + m] = out[m] / cells;
+}
+
+// ... and every cell of member m becomes RN((double)x - mean[m]) (slots that hold no cell stay 0)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_batch_mean_sub(T* __restrict__ x, Geo lg, int64_t slots, int nb,
+                                                           const double* __restrict__ mean)
+{
+    const int m = (int)(blockIdx.x / (unsigned)nb);
+    const int tid = (int)(blockIdx.x - (unsigned)m * nb) * kBlock + (int)threadIdx.x, nt = nb * kBlock;
+    const MGeo g = mgeo(lg);
+    T* const xm = x + (int64_t)m * slots;
+    const double mu = mean[m];
+    for (int s = tid; s < g.nz * g.P; s += nt) {
+        int i, j, k;
+        if (slot_of(s, g, i, j, k)) xm[s] = (T)((double)xm[s] - mu);
+    }
 }
 
 // partials[blockIdx.x] = sum (f - A u)^2, partials[total + blockIdx.x] = sum f^2 over the workgroup's cells
@@ -488,12 +522,6 @@ Geo member_geo(int64_t nx, int64_t ny, int64_t nz)
     return g;
 }
 
-double coarse_coef(int coarse_bc, int level)
-{
-    if (coarse_bc != MGP_BC_CONSISTENT || level <= 0) return 0.0;
-    const double p = std::ldexp(1.0, level);
-    return (p - 1.0) / (p + 1.0);
-}
 
 struct BHostLevel {
     Geo g;
@@ -1200,6 +1228,33 @@ int mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm)
         if (rnorm) rnorm[m] = std::sqrt(h[m]);
         if (fnorm) fnorm[m] = std::sqrt(h[b->B + m]);
     }
+    return MGP_OK;
+}
+
+int mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (level < 0 || level >= (int)b->lev.size()) return b->fail(MGP_ERR_ARG, "level %d out of range", level);
+    if (which != MGP_FIELD_U && which != MGP_FIELD_F)
+        return b->fail(MGP_ERR_ARG, "mgp_batch_remove_mean: which must be MGP_FIELD_U or MGP_FIELD_F");
+    const BHostLevel& L = b->lev[level];
+    char* const base = which == MGP_FIELD_U ? L.u : L.f;
+    const int nb = piece_blocks(L.slots);
+    const unsigned grid = (unsigned)((int64_t)b->B * nb);
+    if (b->rb == 4) {
+        mgp::k_batch_mean_sum<float><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const float*)base, L.g, L.slots,
+                                                                                     (double)L.cells, b->B, b->d_norm);
+        mgp::k_batch_mean_sub<float><<<dim3(grid), dim3(kBlock), 0, b->s>>>((float*)base, L.g, L.slots, nb, b->d_norm + b->B);
+    } else {
+        mgp::k_batch_mean_sum<double><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const double*)base, L.g, L.slots,
+                                                                                      (double)L.cells, b->B, b->d_norm);
+        mgp::k_batch_mean_sub<double><<<dim3(grid), dim3(kBlock), 0, b->s>>>((double*)base, L.g, L.slots, nb, b->d_norm + b->B);
+    }
+    BHIP(b, hipGetLastError());
+    std::vector<double> h((size_t)b->B);
+    BHIP(b, hipMemcpyAsync(h.data(), b->d_norm + b->B, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b->s));
+    BHIP(b, hipStreamSynchronize(b->s));
+    if (means) std::copy(h.begin(), h.end(), means);
     return MGP_OK;
 }
 

@@ -37,7 +37,7 @@ __device__ __forceinline__ int64_t half_item(const T* other, const T* __restrict
     }
     const int nb = (i == 0) + (i == g.nx - 1) + (j == 0) + (j == g.ny - 1) +
                    (DIM == 3 ? (gk == 0) + (gk == g.gnz - 1) : 0);
-    *v = (T)op.relax(s, (C)f[own], nb);
+    *v = (T)op.relax_z(s, (C)f[own], nb);
     dst[own] = *v;
     return own;
 }

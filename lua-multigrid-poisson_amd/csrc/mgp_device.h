@@ -150,6 +150,19 @@ struct Op {
         if (cl != (T)0 && nb != 0) return div_rn(a, sel(dg, nb), sel(ydg, nb));
         return div_rn(a, adiag, yadiag);
     }
+    // relax for the kernels that can hold a one-cell level (the scalar per-cell forms, the coarse tail, the batch,
+    // k_gslex): under MGP_BC_NEUMANN (cl = -1) that cell's diagonal dg[2 DIM] is 0, and a cell whose diagonal is 0 is
+    // relaxed to +0 whatever f holds (div_rn(a, 0, .) would give -0 or NaN).  Every other cell: relax's bits.
+    __device__ __forceinline__ T relax_z(T sum, T fc, int nb) const
+    {
+        const T a = fc - sum * inv_hSq;
+        if (cl != (T)0 && nb != 0) {
+            const T d = sel(dg, nb);
+            const T q = div_rn(a, d, sel(ydg, nb));
+            return d == (T)0 ? (T)0 : q;
+        }
+        return div_rn(a, adiag, yadiag);
+    }
     // f - (sum/h^2 + diag*u)
     __device__ __forceinline__ T residual(T sum, T fc, T uc, int nb) const
     {
@@ -239,7 +252,8 @@ Op<T, DIM> make_op(double h, double cl)
     op.cl = (T)cl;
     for (int nb = 0; nb <= 2 * DIM; ++nb) {
         op.dg[nb] = nb == 0 ? op.adiag : ((T)(-2 * DIM) - (T)nb * op.cl) / op.hSq;
-        op.ydg[nb] = (T)1 / op.dg[nb];
+        // (a zero diagonal, the one-cell level under cl = -1: never divided by, see relax_z; no inf in the table)
+        op.ydg[nb] = op.dg[nb] == (T)0 ? (T)0 : (T)1 / op.dg[nb];
     }
     return op;
 }

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(gsl_threads<DIM>()) void k_gslex(T* __restrict__ u,
                 sum = sum + (C)s[c - E * E];
                 sum = sum + (C)s[c + E * E];
             }
-            s[c] = (T)op.relax(sum, (C)fc, nb);
+            s[c] = (T)op.relax_z(sum, (C)fc, nb);
         }
         __syncthreads();
     }

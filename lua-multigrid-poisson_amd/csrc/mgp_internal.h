@@ -1,13 +1,27 @@
 // mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4 kernel units:
 // mgp_kernels.hip (one launch per piece; k_zs's stage-split variants and the 2D k_ys), mgp_zs.hip / mgp_zs_f64.hip (k_zs, the fused
 // phases' planning and dispatch), mgp_tail.hip (coarse tail), mgp_blk.hip / mgp_blk2.hip (tiled phases), mgp_gslex.hip,
-// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip.  The last block holds what the kernel units
+// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip.  The last block holds what the kernel units
 // call in each other.  Not part of the public ABI (include/mgpoisson.h is).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 
 namespace mgp {
+
+// The boundary coefficient c_l of level `level` (ghost = -c_l * boundary cell) for mgp_opts.coarse_bc: the ONE rule
+// every reader of cl follows (engine selection, z-chunk planning, the tail, the field views, the norms, the pieces,
+// the batch).  0 MGP_BC_ZERO: 0; 1 MGP_BC_CONSISTENT: 0 on level 0, (2^l - 1) / (2^l + 1) below; 2 MGP_BC_FACE: +1
+// and 3 MGP_BC_NEUMANN: -1 on every level.
+inline double coarse_coef(int coarse_bc, int level)
+{
+    if (coarse_bc == 2) return 1.0;
+    if (coarse_bc == 3) return -1.0;
+    if (coarse_bc != 1 || level <= 0) return 0.0;
+    const double p = std::ldexp(1.0, level);
+    return (p - 1.0) / (p + 1.0);
+}
 
 constexpr int kGhost3D = 1;  // ghost planes per side of every 3D level
 // ... when a slab-distributed level runs the temporally blocked phases (k_zs): PRE reads 5 planes
@@ -157,8 +171,8 @@ hipError_t launch_sum_partials(const double* partials, int n, double* out, hipSt
 
 // Mixed-precision defect correction on level 0 (mgp_refine.hip, mgp_refine_*): fp64 psi64 / f64 in level 0's packed
 // layout (same element offsets and ghost planes as the fp32 fields; pointers to interior plane 0).
-// launch_defect: r = f64 - A psi64 in double (Op<double, DIM>::residual, cl = 0, ghost 0: bit for bit
-// launch_residual_field(rb = 8)), (float)r to r32, +0.0f to u32_or_null when set (every packed slot, as a memset
+// launch_defect: r = f64 - A psi64 in double (Op<double, DIM>::residual with level 0's cl: bit for bit
+// launch_residual_field(rb = 8); cl != 0 runs an instantiation of its own), (float)r to r32, +0.0f to u32_or_null when set (every packed slot, as a memset
 // would leave it); out[0] = sum r^2 (before narrowing), out[1] = sum f64^2, fp64 in fixed order.
 // launch_refine_add: psi64 += (double)e32 over the interior planes; out[0] = sum e32^2.
 // partials: refine_partials() doubles.  Rows of >= 4 cells take the 16-byte form (grid-stride and XCD-banded from
@@ -167,11 +181,20 @@ int defect_blocks(Geo g);
 int refine_add_blocks(Geo g);
 int refine_partials();
 hipError_t launch_defect(int dim, const double* psi64, const double* f64, float* r32, float* u32_or_null, Geo g,
-                         double h, double* partials, double* out, hipStream_t s);
+                         double h, double cl, double* partials, double* out, hipStream_t s);
 hipError_t launch_refine_add(double* psi64, const float* e32, Geo g, double* partials, double* out, hipStream_t s);
 // exact widening / round-to-nearest narrowing of n packed reals
 hipError_t launch_refine_widen(const float* src, double* dst, int64_t n, hipStream_t s);
 hipError_t launch_refine_narrow(const double* src, float* dst, int64_t n, hipStream_t s);
+
+// Removing a field's mean (mgp_mean.hip, mgp_remove_mean / mgp_refine_remove_mean).  p: interior plane 0 of a packed
+// field of layout g, rb = 4 / 8.  launch_mean_sum: out[0] = the fp64 sum of this rank's cells in a fixed order (per
+// wave, per workgroup, then launch_sum_partials); pad slots, ghost planes and the empty slots of nx = 1 rows do not
+// enter it.  partials: kSumBlocks doubles.  launch_mean_sub: out[1] = out[0] / cells (the global count; out[0] all-
+// reduced first on a distributed level), then every cell becomes RN((double)x - out[1]), 16 bytes per access where
+// the rows allow.
+hipError_t launch_mean_sum(int rb, const void* p, Geo g, double* partials, double* out, hipStream_t s);
+hipError_t launch_mean_sub(int rb, void* p, Geo g, double cells, double* out, hipStream_t s);
 
 // Temporally blocked smoothing phases of a replicated 3D red/black level (ns = 2 sweeps):
 //   pre : dst = nu1 sweeps of src; R (coarse packed, Geo gc) = restrict(residual(dst))

@@ -1,8 +1,9 @@
 // mgp_refine.hip — the two fp64 / fp32 streaming passes of mixed-precision defect correction on the finest
 // level (mgp_refine_*; the outer loop cpu.lua:196-216 with real = 'double', around fp32 cycles):
-//   k_defect      r = f - A psi in double from the fp64 psi and f (Op<double, DIM>::residual, cl = 0, ghost 0:
-//                 bit for bit launch_residual_field(rb = 8)), stored as (float)r at the same packed slot of the
-//                 fp32 level-0 f; sum r^2 (before narrowing) and sum f^2 in fp64; optionally +0.0f to the fp32 u
+//   k_defect      r = f - A psi in double from the fp64 psi and f (Op<double, DIM>::residual with level 0's cl:
+//                 bit for bit launch_residual_field(rb = 8); CL = false is the cl = 0 pass, CL = true a separate
+//                 instantiation with the boundary-modified diagonal of MGP_BC_FACE / _NEUMANN), stored as (float)r
+//                 at the same packed slot of the fp32 level-0 f; sum r^2 (before narrowing) and sum f^2 in fp64; optionally +0.0f to the fp32 u
 //                 (the zero guess of the inner cycles).  24 B per cell: read psi and f, write r32 and u32.
 //   k_refine_add  psi += (double)e from the fp32 level-0 u, sum e^2 in fp64.  20 B per cell.
 // The fp64 fields have level 0's packed red/black layout (Geo / pidx), so a cell has one index in all four arrays.
@@ -53,9 +54,10 @@ struct DefectIn {
     double edge;
     int64_t own;
     int o;
+    int nbyz, i0;  // CL: the cells' y / z faces on the box, x of the first cell
 };
 
-template <int DIM>
+template <int DIM, bool CL>
 __device__ __forceinline__ void defect_load(DefectIn& in, const double* __restrict__ psi, const double* __restrict__ f,
                                             const Geo& g, int64_t it)
 {
@@ -85,11 +87,16 @@ __device__ __forceinline__ void defect_load(DefectIn& in, const double* __restri
     in.uc = vload<double, 2>(psi + own);
     in.own = own;
     in.o = o;
+    if (CL) {
+        const int64_t gk = g.z0 + k;
+        in.nbyz = (j == 0) + (j == g.ny - 1) + (DIM == 3 ? (gk == 0) + (gk == g.gnz - 1) : 0);
+        in.i0 = 2 * m0 + o;
+    }
 }
 
-template <int DIM, bool ZERO>
+template <int DIM, bool ZERO, bool CL>
 __device__ __forceinline__ void defect_store(const DefectIn& in, float* __restrict__ r32, float* __restrict__ u32,
-                                             const Op<double, DIM>& op, double& rr, double& ff)
+                                             const Op<double, DIM>& op, const Geo& g, double& rr, double& ff)
 {
     const int o = in.o;
     F2 out;
@@ -104,7 +111,12 @@ __device__ __forceinline__ void defect_store(const DefectIn& in, float* __restri
             sm = sm + in.zl.v[e];
             sm = sm + in.zr.v[e];
         }
-        const double r = op.residual(sm, in.fv.v[e], in.uc.v[e], 0);
+        int nb = 0;
+        if (CL) {
+            const int i = in.i0 + 2 * e;
+            nb = in.nbyz + (i == 0) + (i == g.nx - 1);
+        }
+        const double r = op.residual(sm, in.fv.v[e], in.uc.v[e], nb);
         out.v[e] = (float)r;
         rr = __builtin_fma(r, r, rr);
         ff = __builtin_fma(in.fv.v[e], in.fv.v[e], ff);
@@ -113,7 +125,7 @@ __device__ __forceinline__ void defect_store(const DefectIn& in, float* __restri
     if (ZERO) vstore<float, 2>(u32 + in.own, vzero<float, 2>());
 }
 
-template <int DIM, bool ZERO>
+template <int DIM, bool ZERO, bool CL>
 __global__ __launch_bounds__(kBlock) void k_defect(const double* __restrict__ psi, const double* __restrict__ f,
                                                    float* __restrict__ r32, float* __restrict__ u32, Geo g,
                                                    Op<double, DIM> op, int64_t items, double* __restrict__ partials,
@@ -124,15 +136,15 @@ __global__ __launch_bounds__(kBlock) void k_defect(const double* __restrict__ ps
     double rr = 0.0, ff = 0.0;
     if (it < items) {
         DefectIn in;
-        defect_load<DIM>(in, psi, f, g, it);
-        defect_store<DIM, ZERO>(in, r32, u32, op, rr, ff);
+        defect_load<DIM, CL>(in, psi, f, g, it);
+        defect_store<DIM, ZERO, CL>(in, r32, u32, op, g, rr, ff);
     }
     block_pair(rr, ff, partials, fofs);
 }
 
 // Grid-stride form for large levels (gridDim.x a multiple of 8): the workgroups of XCD x (b % 8 == x) sweep the
 // contiguous band x of the items, so y / z neighbours meet in that XCD's L2; two items' loads in flight per thread.
-template <int DIM, bool ZERO>
+template <int DIM, bool ZERO, bool CL>
 __global__ __launch_bounds__(kBlock) void k_defect_gs(const double* __restrict__ psi, const double* __restrict__ f,
                                                       float* __restrict__ r32, float* __restrict__ u32, Geo g,
                                                       Op<double, DIM> op, int64_t items, double* __restrict__ partials,
@@ -147,17 +159,17 @@ __global__ __launch_bounds__(kBlock) void k_defect_gs(const double* __restrict__
     for (int64_t i0 = base + (int64_t)(blockIdx.x >> 3) * kBlock + threadIdx.x; i0 < end; i0 += 2 * step) {
         const int64_t i1 = i0 + step;
         DefectIn a, c;
-        defect_load<DIM>(a, psi, f, g, i0);
-        if (i1 < end) defect_load<DIM>(c, psi, f, g, i1);
-        defect_store<DIM, ZERO>(a, r32, u32, op, rr, ff);
-        if (i1 < end) defect_store<DIM, ZERO>(c, r32, u32, op, rr, ff);
+        defect_load<DIM, CL>(a, psi, f, g, i0);
+        if (i1 < end) defect_load<DIM, CL>(c, psi, f, g, i1);
+        defect_store<DIM, ZERO, CL>(a, r32, u32, op, g, rr, ff);
+        if (i1 < end) defect_store<DIM, ZERO, CL>(c, r32, u32, op, g, rr, ff);
     }
     block_pair(rr, ff, partials, fofs);
 }
 
 // Scalar form for rows of one or two cells (hw < 2, nx = 1 included): a thread per packed slot, grid-stride.
 // The empty slot of an nx = 1 row holds no cell: r32 = u32 = 0 there.
-template <int DIM, bool ZERO>
+template <int DIM, bool ZERO, bool CL>
 __global__ __launch_bounds__(kBlock) void k_defect_s(const double* __restrict__ psi, const double* __restrict__ f,
                                                      float* __restrict__ r32, float* __restrict__ u32, Geo g,
                                                      Op<double, DIM> op, double* __restrict__ partials, int fofs)
@@ -182,7 +194,13 @@ __global__ __launch_bounds__(kBlock) void k_defect_s(const double* __restrict__ 
                 sm = sm + psi[oth + g.P];
             }
             const double fc = f[s];
-            const double r = op.residual(sm, fc, psi[s], 0);
+            int nb = 0;
+            if (CL) {
+                const int64_t gk = g.z0 + k;
+                nb = (i == 0) + (i == g.nx - 1) + (j == 0) + (j == g.ny - 1) +
+                     (DIM == 3 ? (gk == 0) + (gk == g.gnz - 1) : 0);
+            }
+            const double r = op.residual(sm, fc, psi[s], nb);
             out = (float)r;
             rr = __builtin_fma(r, r, rr);
             ff = __builtin_fma(fc, fc, ff);
@@ -240,19 +258,19 @@ bool defect_vector(const Geo& g) { return g.hw >= 2; }
 int64_t defect_items(const Geo& g) { return (g.H / 2) * 2 * g.nz; }
 bool defect_gs(const Geo& g) { return defect_vector(g) && defect_items(g) >= (int64_t)kDefectGsBlocks * kBlock * 2; }
 
-template <int DIM, bool ZERO>
-void defect_t(const double* psi, const double* f, float* r32, float* u32, Geo g, double h, double* partials,
+template <int DIM, bool ZERO, bool CL>
+void defect_t(const double* psi, const double* f, float* r32, float* u32, Geo g, double h, double cl, double* partials,
               hipStream_t s)
 {
-    const Op<double, DIM> op = make_op<double, DIM>(h, 0.0);
+    const Op<double, DIM> op = make_op<double, DIM>(h, cl);
     const int fofs = kDefectMaxBlocks;
     if (defect_gs(g)) {
-        k_defect_gs<DIM, ZERO><<<kDefectGsBlocks, kBlock, 0, s>>>(psi, f, r32, u32, g, op, defect_items(g), partials, fofs);
+        k_defect_gs<DIM, ZERO, CL><<<kDefectGsBlocks, kBlock, 0, s>>>(psi, f, r32, u32, g, op, defect_items(g), partials, fofs);
     } else if (defect_vector(g)) {
         const int64_t items = defect_items(g);
-        k_defect<DIM, ZERO><<<nblk(items), kBlock, 0, s>>>(psi, f, r32, u32, g, op, items, partials, fofs);
+        k_defect<DIM, ZERO, CL><<<nblk(items), kBlock, 0, s>>>(psi, f, r32, u32, g, op, items, partials, fofs);
     } else {
-        k_defect_s<DIM, ZERO><<<(unsigned)defect_blocks(g), kBlock, 0, s>>>(psi, f, r32, u32, g, op, partials, fofs);
+        k_defect_s<DIM, ZERO, CL><<<(unsigned)defect_blocks(g), kBlock, 0, s>>>(psi, f, r32, u32, g, op, partials, fofs);
     }
 }
 
@@ -273,15 +291,23 @@ int refine_add_blocks(Geo g)
 
 int refine_partials() { return std::max(2 * kDefectMaxBlocks, kAddMaxBlocks); }
 
+template <int DIM, bool CL>
+static void defect_d(const double* psi64, const double* f64, float* r32, float* u32_or_null, Geo g, double h, double cl,
+                     double* partials, hipStream_t s)
+{
+    if (u32_or_null) defect_t<DIM, true, CL>(psi64, f64, r32, u32_or_null, g, h, cl, partials, s);
+    else defect_t<DIM, false, CL>(psi64, f64, r32, nullptr, g, h, cl, partials, s);
+}
+
 hipError_t launch_defect(int dim, const double* psi64, const double* f64, float* r32, float* u32_or_null, Geo g,
-                         double h, double* partials, double* out, hipStream_t s)
+                         double h, double cl, double* partials, double* out, hipStream_t s)
 {
     if (dim == 3) {
-        if (u32_or_null) defect_t<3, true>(psi64, f64, r32, u32_or_null, g, h, partials, s);
-        else defect_t<3, false>(psi64, f64, r32, nullptr, g, h, partials, s);
+        if (cl == 0.0) defect_d<3, false>(psi64, f64, r32, u32_or_null, g, h, cl, partials, s);
+        else defect_d<3, true>(psi64, f64, r32, u32_or_null, g, h, cl, partials, s);
     } else {
-        if (u32_or_null) defect_t<2, true>(psi64, f64, r32, u32_or_null, g, h, partials, s);
-        else defect_t<2, false>(psi64, f64, r32, nullptr, g, h, partials, s);
+        if (cl == 0.0) defect_d<2, false>(psi64, f64, r32, u32_or_null, g, h, cl, partials, s);
+        else defect_d<2, true>(psi64, f64, r32, u32_or_null, g, h, cl, partials, s);
     }
     const int nb = defect_blocks(g);
     (void)launch_sum_partials(partials, nb, out, s);

@@ -289,7 +289,11 @@ __device__ __forceinline__ void tc_half(T* U, const T* F, const Op<T, DIM>& op, 
                 sm = sm + U[x - L::SZ];
                 sm = sm + U[x + L::SZ];
             }
-            U[x] = op.relax_idx(sm, F[x], L::nb(0, j, k));
+            const T rv = op.relax_idx(sm, F[x], L::nb(0, j, k));
+            if constexpr (CNT == 1)  // the one-cell level: under cl = -1 its diagonal is 0 and the cell is relaxed to +0
+                U[x] = op.dg[2 * DIM] == (T)0 ? (T)0 : rv;
+            else
+                U[x] = rv;
         }
     }
 }

@@ -39,7 +39,12 @@ loop over that step; mg:twoGrid raises; mg:refineResidual() returns ||f - A psi|
 fields.  One GPU only (ngpu > 1 raises).
 Extra table fields select the build's configurations: dim (2|3), real, smoother ('jacobi'|'rbgs'|'gs_lex'),
 cycle ('V'|'F'), prolong ('pc'|'linear'), coarse_init ('fresh'|'warm'), coarse_bc
-('zero'|'consistent'), restriction ('average'|'full_weighting'), arith ('real'|'double'), device.
+('zero'|'consistent'|'face'|'neumann'), restriction ('average'|'full_weighting'), arith ('real'|'double'), device.
+boundary = 'ghost' | 'face' | 'neumann' (this build's addition, default 'ghost' = the reference's box, the ghost cell
+centre at 0): 'face' holds u = 0 on the box face, 'neumann' du/dn = 0 there (the ghost the reference carries commented
+out, cpu.lua:28-31), on every level; an error together with a coarse_bc other than 'zero'.  Under 'neumann' psi is
+determined up to a constant and f must sum to 0: mg:solve() removes f's mean before its first step and psi's after
+its last one (mg:removeMean('f' | 'psi'), mgp_remove_mean); mg:step() does neither.
 Defaults reproduce cpu.lua
 (2D, double, Jacobi 7+7, V-cycle, injection, 2x2 average, fresh zero coarse guess, ghost value 0).
 Errors from the library raise Lua errors (error()), as the reference's own failures do.
@@ -95,6 +100,10 @@ int         mgp_set_coarse_handoff(mgp_ctx* c, int64_t size, mgp_coarse_fn fn, v
 int         mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* frob);
 int         mgp_set_debug(mgp_ctx* c, int mode);
 int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm);
+int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
+int         mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean);
+int         mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean);
+int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
 int         mgp_refine_begin(mgp_ctx* c);
 int         mgp_refine_end(mgp_ctx* c);
 int         mgp_refine_set(mgp_ctx* c, int which, const double* src, int64_t count, int mem);
@@ -135,12 +144,23 @@ local CODES = {
 	cycle = {V = 0, F = 1},
 	prolong = {pc = 0, linear = 1},
 	coarse_init = {fresh = 0, warm = 1},
-	coarse_bc = {zero = 0, consistent = 1},
+	coarse_bc = {zero = 0, consistent = 1, face = 2, neumann = 3},
 	restriction = {average = 0, full_weighting = 1},
 	arith = {real = 0, double = 1},
 }
 -- include/mgpoisson.h MGP_FIELD_*; names of cpu-raw.lua:148-171
 local FIELD = {psi = 0, f = 1, rs = 2, vs = 3, psiOld = 4, errorBuf = 5, tmpU = 6, Vs = 0, Rs = 1}
+
+-- the `boundary` field of the table protocols -> boundary, coarse_bc
+local function boundaryOf(a)
+	local b = a.boundary or 'ghost'
+	if b ~= 'ghost' and b ~= 'face' and b ~= 'neumann' then error("boundary: 'ghost' | 'face' | 'neumann'", 3) end
+	if b == 'ghost' then return b, a.coarse_bc end
+	if a.coarse_bc ~= nil and a.coarse_bc ~= 'zero' then
+		error("boundary = '" .. b .. "' sets the boundary of every level: it does not combine with coarse_bc", 3)
+	end
+	return b, b
+end
 
 local function check(rc, ctx)
 	if rc < 0 then error('libmgpoisson: ' .. ffi.string(lib.mgp_last_error(ctx)), 3) end
@@ -310,9 +330,11 @@ function MultigridHIP:init(a, real, cpuDepth, engine)
 		smoother = (v == MultigridHIP.GaussSeidel) and 'gs_lex' or
 			((v == MultigridHIP.RedBlackGaussSeidel) and 'rbgs' or 'jacobi')
 	end
+	local boundary, bc = boundaryOf(args)
+	rawset(self, 'boundary', boundary)
 	rawset(self, 'build', {real = rawget(self, 'real'), smooth = args.smooth or MultigridHIP.smooth,
 		smoother = smoother or 'jacobi', cycle = args.cycle, prolong = args.prolong,
-		coarse_init = args.coarse_init, coarse_bc = args.coarse_bc, restriction = args.restriction,
+		coarse_init = args.coarse_init, coarse_bc = bc, restriction = args.restriction,
 		arith = args.arith, device = args.device})
 	local cells = n * n * (dim == 3 and n or 1)
 	rawset(self, 'count', cells)
@@ -380,6 +402,17 @@ function MultigridHIP:residualNorm(level)
 	if g then checkGroup(lib.mgp_group_residual_norm(g, level or 0, r, f), g)
 	else check(lib.mgp_residual_norm(self.ctx, level or 0, r, f), self.ctx) end
 	return r[0], f[0]
+end
+
+-- subtract the mean of 'psi' or 'f' (level 0 by default) on the device; returns it (mgp_remove_mean)
+function MultigridHIP:removeMean(which, level)
+	local m = ffi.new('double[1]')
+	local g = rawget(self, 'group')
+	if rawget(self, 'mixed') and (level or 0) == 0 then
+		check(lib.mgp_refine_remove_mean(self.ctx, FIELD[which or 'psi'], m), self.ctx)  -- MGP_REFINE_PSI / _F = 0 / 1
+	elseif g then checkGroup(lib.mgp_group_remove_mean(g, level or 0, FIELD[which or 'psi'], m), g)
+	else check(lib.mgp_remove_mean(self.ctx, level or 0, FIELD[which or 'psi'], m), self.ctx) end
+	return m[0]
 end
 
 -- real = 'mixed': ||f - A psi||, ||f|| of the double fields
@@ -462,11 +495,14 @@ local function finite(x) return x == x and x ~= math.huge and x ~= -math.huge en
 -- cpu.lua:208-216, break rules included
 function MultigridHIP:solve()
 	if self.debug then print('#iter', 'err') end
+	local neumann = rawget(self, 'boundary') == 'neumann'
+	if neumann then self:removeMean('f') end
 	for iter = 1, self.maxiter do
 		local err = self:step()
 		if self.errorCallback and self.errorCallback(iter, err) then break end
 		if err < self.epsilon or not finite(err) then break end
 	end
+	if neumann then self:removeMean('psi') end
 end
 
 -- cpu-raw.lua:239-258 / gpu.lua:348-373: two outer iterations
@@ -526,9 +562,11 @@ setmetatable(MGBatch, {
 		self.n, self.dim, self.batch = assert(a.size), a.dim or 2, assert(a.batch)
 		if a.maxiter ~= nil then self.maxiter = a.maxiter end
 		if a.epsilon ~= nil then self.epsilon = a.epsilon end
+		local boundary, bc = boundaryOf(a)
+		self.boundary = boundary
 		self.build = {real = a.real or 'double', smooth = a.smooth or cls.smooth,
 			smoother = a.inPlaceIterativeSolver or a.smoother or 'jacobi', cycle = a.cycle, prolong = a.prolong,
-			coarse_init = a.coarse_init, coarse_bc = a.coarse_bc, device = a.device}
+			coarse_init = a.coarse_init, coarse_bc = bc, device = a.device}
 		local o = MultigridHIP.makeOpts(self)
 		local out = ffi.new('mgp_batch*[1]')
 		checkBatch(lib.mgp_batch_create(out, o, self.batch), nil)
@@ -566,9 +604,19 @@ end
 
 function MGBatch:step() return self:cycles(1) end
 
--- cpu.lua:208-216 per member: fills self.iters[m] and self.err[m]
+-- every member's own mean subtracted from its 'psi' or 'f' of a level; returns the B means
+function MGBatch:removeMean(which, level)
+	local m = ffi.new('double[?]', self.batch)
+	checkBatch(lib.mgp_batch_remove_mean(self.handle, level or 0, FIELD[which or 'psi'], m), self.handle)
+	return m
+end
+
+-- cpu.lua:208-216 per member: fills self.iters[m] and self.err[m] (boundary = 'neumann': f's mean removed first,
+-- psi's after the solve)
 function MGBatch:solve()
+	if self.boundary == 'neumann' then self:removeMean('f') end
 	checkBatch(lib.mgp_batch_solve(self.handle, self.epsilon, self.maxiter, self.iters, self.err), self.handle)
+	if self.boundary == 'neumann' then self:removeMean('psi') end
 end
 
 function MGBatch:residualNorm()

@@ -37,7 +37,7 @@ JACOBI, RBGS, GS_LEX = 0, 1, 2
 CYCLE_V, CYCLE_F = 0, 1
 PROLONG_PC, PROLONG_LINEAR = 0, 1
 COARSE_FRESH, COARSE_WARM = 0, 1
-BC_ZERO, BC_CONSISTENT = 0, 1
+BC_ZERO, BC_CONSISTENT, BC_FACE, BC_NEUMANN = 0, 1, 2, 3
 RESTRICT_AVERAGE, RESTRICT_FULL_WEIGHTING = 0, 1
 ARITH_REAL, ARITH_DOUBLE = 0, 1
 API_VERSION = 3
@@ -122,6 +122,10 @@ SIGNATURES = {
     "mgp_metrics": (ctypes.c_int, [_vp, _P(_dbl), _P(_i64), _P(_dbl)]),
     "mgp_set_coarse_level": (ctypes.c_int, [_vp, _i64]),
     "mgp_residual_norm": (ctypes.c_int, [_vp, ctypes.c_int, _P(_dbl), _P(_dbl)]),
+    "mgp_remove_mean": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(_dbl)]),
+    "mgp_refine_remove_mean": (ctypes.c_int, [_vp, ctypes.c_int, _P(_dbl)]),
+    "mgp_group_remove_mean": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(_dbl)]),
+    "mgp_batch_remove_mean": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _P(_dbl)]),
     "mgp_refine_begin": (ctypes.c_int, [_vp]),
     "mgp_refine_end": (ctypes.c_int, [_vp]),
     "mgp_refine_set": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64, ctypes.c_int]),

@@ -16,7 +16,7 @@ SMOOTHERS = {"jacobi": L.JACOBI, "rbgs": L.RBGS, "gs_lex": L.GS_LEX}
 CYCLES = {"V": L.CYCLE_V, "F": L.CYCLE_F}
 PROLONGS = {"pc": L.PROLONG_PC, "linear": L.PROLONG_LINEAR}
 COARSE_INITS = {"fresh": L.COARSE_FRESH, "warm": L.COARSE_WARM}
-COARSE_BCS = {"zero": L.BC_ZERO, "consistent": L.BC_CONSISTENT}
+COARSE_BCS = {"zero": L.BC_ZERO, "consistent": L.BC_CONSISTENT, "face": L.BC_FACE, "neumann": L.BC_NEUMANN}
 RESTRICTIONS = {"average": L.RESTRICT_AVERAGE, "full_weighting": L.RESTRICT_FULL_WEIGHTING}
 REALS = {"double": 8, "float": 4}
 # real = float arithmetic: "real" = every operation in float (gpu.lua:32), "double" = float buffers with every
@@ -250,6 +250,19 @@ class Context:
         self._chk(L.lib.mgp_residual_norm(self._h, level, ctypes.byref(r), ctypes.byref(f)))
         return r.value, f.value
 
+    def remove_mean(self, level=0, which=L.FIELD_U) -> float:
+        """Subtract the mean (fp64 sum in a fixed order, all-reduced on a slab level) from a level's u or f; returns
+        it.  A Neumann box needs f's mean removed before the first cycle and psi's after the last one."""
+        m = ctypes.c_double()
+        self._chk(L.lib.mgp_remove_mean(self._h, int(level), int(which), ctypes.byref(m)))
+        return m.value
+
+    def refine_remove_mean(self, which) -> float:
+        """remove_mean of the refinement's fp64 psi (REFINE_PSI) or f (REFINE_F)."""
+        m = ctypes.c_double()
+        self._chk(L.lib.mgp_refine_remove_mean(self._h, int(which), ctypes.byref(m)))
+        return m.value
+
     # -- mixed-precision defect correction (mgp_refine_*): fp64 psi / f around the fp32 cycles --
     def refine_begin(self):
         """Start refinement on a real='float' context: fp64 psi / f = the widened level-0 u / f."""
@@ -417,6 +430,11 @@ class Group:
         self._chk(L.lib.mgp_group_residual_norm(self._h, level, ctypes.byref(r), ctypes.byref(f)))
         return r.value, f.value
 
+    def remove_mean(self, level=0, which=L.FIELD_U) -> float:
+        m = ctypes.c_double()
+        self._chk(L.lib.mgp_group_remove_mean(self._h, int(level), int(which), ctypes.byref(m)))
+        return m.value
+
     def field_stats(self, which=L.FIELD_U, level=0):
         h = ctypes.c_uint64()
         d = (ctypes.c_double * 3)()
@@ -555,6 +573,12 @@ class BatchContext:
         self._chk(L.lib.mgp_batch_residual_norm(self._h, r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                                 f.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return r, f
+
+    def remove_mean(self, level=0, which=L.FIELD_U) -> np.ndarray:
+        """Subtract each member's own mean from its u or f of a level; the B means."""
+        m = np.zeros(self.batch, dtype=np.float64)
+        self._chk(L.lib.mgp_batch_remove_mean(self._h, int(level), int(which), m.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return m
 
     def launches(self) -> int:
         """Kernel launches per cycle of the last cycles() / solve() call (independent of B)."""

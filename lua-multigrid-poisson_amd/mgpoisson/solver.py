@@ -99,6 +99,25 @@ class _RawFields:
         return LevelFields(lambda: self.ctx, L.FIELD_U)
 
 
+BOUNDARIES = ("ghost", "face", "neumann")
+
+
+def _boundary(a):
+    """The ``boundary`` keyword of MultigridHIP / MultigridHIPBatch -> (boundary, coarse_bc).  'ghost' (the default)
+    is the reference's box, the ghost cell centre held at 0, with ``coarse_bc`` = 'zero' | 'consistent' as before;
+    'face' holds u = 0 on the box face and 'neumann' du/dn = 0 there, on every level (coarse_bc 'face' / 'neumann'),
+    so neither combines with a ``coarse_bc`` of its own."""
+    b = a.get("boundary") or "ghost"
+    if b not in BOUNDARIES:
+        raise ValueError(f"boundary: {b!r} ('ghost' | 'face' | 'neumann')")
+    bc = a.get("coarse_bc")
+    if b == "ghost":
+        return b, bc or "zero"
+    if bc not in (None, "zero"):
+        raise ValueError(f"boundary={b!r} sets the boundary of every level: it does not combine with coarse_bc={bc!r}")
+    return b, b
+
+
 class MultigridHIP(_RawFields):
     """Drop-in for ``MultigridCPU`` (cpu.lua:15-218), solving on the GPU.
 
@@ -109,6 +128,11 @@ class MultigridHIP(_RawFields):
     ``real``, ``smoother``, ``cycle``, ``prolong``, ``coarse_init``, ``coarse_bc``, ``restriction``)
     default to the reference configuration: 2D, double, Jacobi 7+7, V-cycle, injection, 2x2 average,
     fresh zero guess.
+
+    ``boundary='ghost' | 'face' | 'neumann'`` (this build's addition, default 'ghost' = the reference): u = 0 on the
+    box face, or du/dn = 0 there.  Under 'neumann' psi is determined up to a constant and f must sum to 0 (the point
+    charge of ``init`` does not): ``solve()`` removes f's mean before its first step and psi's after its last one;
+    ``step()`` does neither.
 
     ``real='mixed'`` (this build's addition): ``psi`` / ``f`` are float64, and ``step()`` is one step of
     mixed-precision defect correction (the fp64 defect, ``innerCycles`` fp32 cycles on it from a zero guess, the fp64
@@ -141,9 +165,10 @@ class MultigridHIP(_RawFields):
         self.dim = int(a.get("dim", 2))
         self.size = (n,) * self.dim  # matrix{size, size} (cpu.lua:178)
         sm = a.get("inPlaceIterativeSolver", a.get("smoother", "jacobi"))
+        self.boundary, bc = _boundary(a)
         self._build = dict(dim=self.dim, real=a.get("real", "double"), smoother=_smoother_name(sm),
                            cycle=a.get("cycle", "V"), prolong=a.get("prolong", "pc"),
-                           coarse_init=a.get("coarse_init", "fresh"), coarse_bc=a.get("coarse_bc", "zero"),
+                           coarse_init=a.get("coarse_init", "fresh"), coarse_bc=bc,
                            restriction=a.get("restriction", "average"), device=a.get("device", -1))
         self._ctx = None
         self._ctx_smooth = None
@@ -224,16 +249,28 @@ class MultigridHIP(_RawFields):
             print("err", err)
         return err
 
+    def remove_mean(self, which="psi") -> float:
+        """Subtract the mean of psi or f on the device (mgp_remove_mean; the fp64 fields for real='mixed')."""
+        self._ensure_ctx()
+        if self.mixed:
+            return self._ctx.refine_remove_mean(L.REFINE_PSI if which == "psi" else L.REFINE_F)
+        return self._ctx.remove_mean(0, L.FIELD_U if which == "psi" else L.FIELD_F)
+
     def solve(self):
-        """cpu.lua:208-216, including its break rules."""
+        """cpu.lua:208-216, including its break rules.  boundary='neumann': f's mean is removed first and psi's
+        after the last step."""
         if self.debug:
             print("#iter", "err")
+        if self.boundary == "neumann":
+            self.remove_mean("f")
         for it in range(1, int(self.maxiter) + 1):
             err = self.step()
             if self.errorCallback and self.errorCallback(it, err):
                 break
             if err < self.epsilon or not math.isfinite(err):
                 break
+        if self.boundary == "neumann":
+            self.remove_mean("psi")
 
     def twoGrid(self, h, u, f):
         """cpu.lua:70 twoGrid(h, u, f): u updated in place.  u / f are (L, L[, L]) host arrays, or
@@ -254,7 +291,7 @@ class MultigridHIP(_RawFields):
 class MultigridHIPBatch:
     """``batch`` independent ``MultigridHIP`` problems of one size in one hierarchy (mgp_batch_*; this build's
     addition, the reference solves one box): ``MultigridHIPBatch(size=n, batch=B, ...)`` with MultigridHIP's build
-    keywords.  ``psi`` / ``f`` have shape (B, n, n[, n]); every member starts as cpu.lua:180-193's point charge.
+    keywords (``boundary`` included).  ``psi`` / ``f`` have shape (B, n, n[, n]); every member starts as cpu.lua:180-193's point charge.
     ``step()`` returns the B errs of one outer iteration; ``solve()`` runs cpu.lua:208-216 per member on the device
     and sets ``.iters`` / ``.err`` (B entries each).  ``errorCallback`` is not offered: a host callback per iteration
     would bring back the synchronisation per cycle that batching removes.
@@ -281,10 +318,11 @@ class MultigridHIPBatch:
         self.size = (n,) * self.dim
         self.batch = int(a["batch"])
         sm = a.get("inPlaceIterativeSolver", a.get("smoother", "jacobi"))
+        self.boundary, bc = _boundary(a)
         opts = make_opts(n=(n, n, n if self.dim == 3 else 1), nu1=self.smooth, nu2=self.smooth, dim=self.dim,
                          real=a.get("real", "double"), smoother=_smoother_name(sm), cycle=a.get("cycle", "V"),
                          prolong=a.get("prolong", "pc"), coarse_init=a.get("coarse_init", "fresh"),
-                         coarse_bc=a.get("coarse_bc", "zero"), restriction=a.get("restriction", "average"),
+                         coarse_bc=bc, restriction=a.get("restriction", "average"),
                          device=a.get("device", -1))
         self.ctx = BatchContext(opts, self.batch)
         self.ctx.init_point_charge()
@@ -312,8 +350,13 @@ class MultigridHIPBatch:
         return self.ctx.cycles(1)[0]
 
     def solve(self):
-        """cpu.lua:208-216 per member, on the device."""
+        """cpu.lua:208-216 per member, on the device.  boundary='neumann': every member's f loses its mean first and
+        its psi after the solve."""
+        if self.boundary == "neumann":
+            self.ctx.remove_mean(0, L.FIELD_F)
         self.iters, self.err = self.ctx.solve(self.epsilon, int(self.maxiter))
+        if self.boundary == "neumann":
+            self.ctx.remove_mean(0, L.FIELD_U)
 
 
 def _smoother_name(v):
