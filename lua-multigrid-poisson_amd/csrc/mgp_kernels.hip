@@ -1321,11 +1321,13 @@ __device__ __forceinline__ void zs_split_body(const T* __restrict__ src, const T
         dz.right = col.gm + N == hw;
     }
     // y / z faces of my row at plane q (the generic steps' table index; the steady steps' planes are off the z faces)
+    constexpr bool FAI = ZS_FACE_AS_INTERIOR && !CLZ;  // (timing experiment, see k_zs)
     auto nbyz = [&](int q) {
+        if (FAI) return (gy == 0) + (gy == g.ny - 1);
         return CLZ ? 0 : (gy == 0) + (gy == g.ny - 1) + (z0 + q == 0) + (z0 + q == gnz - 1);
     };
     const int p_end = Z0 + zc + 6;
-    auto inz = [&](int q) { return z0 + q >= 0 && z0 + q < gnz; };  // inside the global box
+    auto inz = [&](int q) { return FAI || (z0 + q >= 0 && z0 + q < gnz); };  // inside the global box
     auto pcl = [&](int q) { return q < qlo ? qlo : (q > qhi ? qhi : q); };
     auto slot = [&](int off, int ns, int q) { return lds + off + (q & (ns - 1)) * SLOT; };
     const int rowpar = (gy + z0) & 1;
@@ -1344,9 +1346,9 @@ __device__ __forceinline__ void zs_split_body(const T* __restrict__ src, const T
     // 4 generic steps saved.
     constexpr bool PART = !CLZ;
     int ps = zlo, pe = p_end;
-    ps = ps > 7 - z0 ? ps : 7 - z0;
+    if (!FAI) ps = ps > 7 - z0 ? ps : 7 - z0;
     ps = ps > qlo + 4 ? ps : qlo + 4;
-    pe = pe < gnz - 1 - z0 ? pe : gnz - 1 - z0;
+    if (!FAI) pe = pe < gnz - 1 - z0 ? pe : gnz - 1 - z0;
     pe = pe < qhi - PFD ? pe : qhi - PFD;
     ps += (UNR - (ps - zlo) % UNR) % UNR;
     if (!PART) pe -= (pe - ps + 1) % UNR;
@@ -1387,7 +1389,7 @@ __device__ __forceinline__ void zs_split_body(const T* __restrict__ src, const T
     const T* const src_black = ZSRC ? nullptr : src + Hh;
     auto prefetch_a = [&](auto st, PF& r, int p) __attribute__((always_inline)) {
         constexpr bool ST = decltype(st)::value;
-        if (ST) {
+        if (ST && !FAI) {
             const int64_t pP = (int64_t)p * P;
             if constexpr (ZSRC)
                 r.u = vzero<T, N>();

@@ -717,6 +717,16 @@ __device__ __forceinline__ void zs_restrict_avg(const T (&rr)[2][N], const T (&x
     }
 }
 
+#ifndef ZS_ALL_GENERIC  // timing experiment: every step generic (the price of the box-face steps)
+#define ZS_ALL_GENERIC 0
+#endif
+// timing experiment only (wrong at the box's z faces): on cl != 0 levels a chunk at a z face runs the steps of an
+// interior chunk (the z-face tests off, the steady loads through the plane clamp): the most that cheaper face steps
+// can win
+#ifndef ZS_FACE_AS_INTERIOR
+#define ZS_FACE_AS_INTERIOR 0
+#endif
+
 template <typename T, bool PRE, int LINEAR, bool ERR, bool CLZ, bool WIDE = false>
 __global__ __launch_bounds__((ZsShape<T, PRE, CLZ, WIDE, PRE && LINEAR == 2>::NTL))
 __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_zs(const T* __restrict__ src, const T* __restrict__ f,
@@ -740,6 +750,10 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     using PF = ZsPrefetch<T, N>;
     constexpr int PFD = PRE ? (CLZ ? ZS_PFD_PRE : ZS_PFD_PRE_CL) : ZS_PFD_POST, NPF = PFD + 1, UNR = NPF == 3 ? 12 : 4;
     static_assert(PFD >= 1 && PFD <= 3, "prefetch distance 1..3");
+    // cl != 0: the generic steps (the box's z faces) take the row's table diagonals (zs_diag), as k_zs_split_cl's do:
+    // bit-identical to relax_direct / residual_direct (mgp_device.h) without their divergent IEEE division
+    constexpr bool TAB = !CLZ;
+    constexpr bool FAI = ZS_FACE_AS_INTERIOR && !CLZ;
     extern __shared__ __align__(16) unsigned char zs_smem[];
     T* const lds = reinterpret_cast<T*>(zs_smem);
     const int tid = threadIdx.x;
@@ -810,7 +824,7 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     }
     // (FWF: the x- and y-combinations of the full weighting follow the residual of plane p - 5 one and two steps later)
     const int p_end = Z0 + zc + (PRE ? (FWF ? 7 : 5) : 3);
-    auto inz = [&](int q) { return z0 + q >= 0 && z0 + q < gnz; };  // inside the global box
+    auto inz = [&](int q) { return FAI || (z0 + q >= 0 && z0 + q < gnz); };  // inside the global box
     auto pcl = [&](int q) { return q < qlo ? qlo : (q > qhi ? qhi : q); };
     // ring slot of plane q (q may be negative; ns = 3 as q mod 3)
     auto slot = [&](int off, int ns, int q) {
@@ -818,7 +832,7 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
         return lds + off + r * SLOT;
     };
     auto nbyz = [&](int q) {
-        return CLZ ? 0 : (gy == 0) + (gy == g.ny - 1) + (z0 + q == 0) + (z0 + q == gnz - 1);
+        return CLZ ? 0 : (gy == 0) + (gy == g.ny - 1) + (FAI ? 0 : (z0 + q == 0) + (z0 + q == gnz - 1));
     };
     const int rowpar = (gy + z0) & 1;
     const int wrole = S::YROLE ? __builtin_amdgcn_readfirstlane(S::wave_role(tid >> 6)) : 0;  // (ZS_YROLE)
@@ -876,7 +890,7 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
         // POST: fine plane 2m + 1 is the first to need coarse plane m + 1; it is loaded with the
         // prefetch of plane 2m and put in the ring at the top of step 2m
         if (!PRE && ((zz0 + p) & 1) == 0) cload(r, ((zz0 + p) >> 1) + 1);
-        if (ST) {  // one 64-bit plane offset, the others by subtraction
+        if (ST && !FAI) {  // one 64-bit plane offset, the others by subtraction
 #ifdef ZS_NOLOAD
             const int64_t pP = 0, Pz = 0;  // every plane reads plane 0
 #else
@@ -1023,24 +1037,24 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
 
         // ---- stages 1..4: half-sweep k on plane p - k (red, black, red, black) ----
         zs_nb_load<T, N>(n1, slot(0, 2, p - 1), col);
-        VT o1 = zs_relax<T, N, CLZ, ST>(W0[sl(2)], W0[sl(1)], W0[sl(ZS_NC ? 3 : 0)], n1, cur.f1, col, par(p - 1), nbyz(p - 1), g.nx, op, dz);
+        VT o1 = zs_relax<T, N, CLZ, ST, TAB>(W0[sl(2)], W0[sl(1)], W0[sl(ZS_NC ? 3 : 0)], n1, cur.f1, col, par(p - 1), nbyz(p - 1), g.nx, op, dz);
         if (!ST && !inz(p - 1)) o1 = vz;
         W1[sl(1)] = o1;
         // (a wave of halo rows d >= 4, role 2, needs stage 1 only: its stages 2..4 would feed no needed cell)
         VT o2 = vz, o3 = vz, o4 = vz;
         if (RO < 2) {
             zs_nb_load<T, N>(n2, slot(S::OFF1, 2, p - 2), col);
-            o2 = zs_relax<T, N, CLZ, ST>(W1[sl(3)], W1[sl(2)], W1[sl(ZS_NC ? 0 : 1)], n2, cur.f2, col, 1 ^ par(p - 2), nbyz(p - 2),
+            o2 = zs_relax<T, N, CLZ, ST, TAB>(W1[sl(3)], W1[sl(2)], W1[sl(ZS_NC ? 0 : 1)], n2, cur.f2, col, 1 ^ par(p - 2), nbyz(p - 2),
                                          g.nx, op, dz);
             if (!ST && !inz(p - 2)) o2 = vz;
             W2[sl(2)] = o2;
             zs_nb_load<T, N>(n3, slot(S::OFF2, 2, p - 3), col);
-            o3 = zs_relax<T, N, CLZ, ST>(W2[sl(4)], W2[sl(3)], W2[sl(ZS_NC ? 1 : 2)], n3, FR[sl(3)], col, par(p - 3), nbyz(p - 3),
+            o3 = zs_relax<T, N, CLZ, ST, TAB>(W2[sl(4)], W2[sl(3)], W2[sl(ZS_NC ? 1 : 2)], n3, FR[sl(3)], col, par(p - 3), nbyz(p - 3),
                                          g.nx, op, dz);
             if (!ST && !inz(p - 3)) o3 = vz;
             W3[sl(3)] = o3;
             zs_nb_load<T, N>(n4, slot(S::OFF3, NS3, p - 4), col);
-            o4 = zs_relax_a<T, N, CLZ, ST>(W3[sl(5)], W3[sl(4)], W3[sl(ZS_NC ? 2 : 3)], n4, FB[sl(4)], col, 1 ^ par(p - 4),
+            o4 = zs_relax_a<T, N, CLZ, ST, TAB>(W3[sl(5)], W3[sl(4)], W3[sl(ZS_NC ? 2 : 3)], n4, FB[sl(4)], col, 1 ^ par(p - 4),
                                            nbyz(p - 4), g.nx, op, dz, AS[RS & 1]);
             if (!ST && !inz(p - 4)) o4 = vz;
             W4[sl(4)] = o4;
@@ -1096,14 +1110,14 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
             }
             // red cells (x parity pq) see black neighbours, black cells (x parity 1 - pq) red ones
             T rred[N], rblk[N], rr[2][N];  // rr: [x parity][e]
-            zs_residual<T, N, CLZ, ST>(W4[sl(6)], W4[sl(5)], W4[sl(ZS_NC ? 3 : 4)], nk, W3[sl(5)], FR[sl(5)], col, pq, nbyz(q), g.nx, op,
+            zs_residual<T, N, CLZ, ST, TAB>(W4[sl(6)], W4[sl(5)], W4[sl(ZS_NC ? 3 : 4)], nk, W3[sl(5)], FR[sl(5)], col, pq, nbyz(q), g.nx, op,
                                    dz, rred);
             // the black cells' neighbours are the red cells of the last step's stage 4 (its askew, ZS_RASK)
             if (kZsRask)
-                zs_residual_a<T, N, CLZ, ST>(AS[(RS & 1) ^ 1], W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q), g.nx, op, dz,
+                zs_residual_a<T, N, CLZ, ST, TAB>(AS[(RS & 1) ^ 1], W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q), g.nx, op, dz,
                                              rblk);
             else
-                zs_residual<T, N, CLZ, ST>(W3[sl(6)], W3[sl(5)], W3[sl(4)], nr, W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q),
+                zs_residual<T, N, CLZ, ST, TAB>(W3[sl(6)], W3[sl(5)], W3[sl(4)], nr, W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q),
                                            g.nx, op, dz, rblk);
 #pragma unroll
             for (int e = 0; e < N; ++e) {
@@ -1122,13 +1136,13 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
             if (!kZsRask) zs_nb_load<T, N>(nr, slot(S::OFF3, NS3, q), col);
             zs_nb_load<T, N>(nk, slot(S::OFF4, 2, q), col);
             T rred[N], rblk[N];
-            zs_residual<T, N, CLZ, ST>(W4[sl(6)], W4[sl(5)], W4[sl(ZS_NC ? 3 : 4)], nk, W3[sl(5)], FR[sl(5)], col, pq, nbyz(q), g.nx, op,
+            zs_residual<T, N, CLZ, ST, TAB>(W4[sl(6)], W4[sl(5)], W4[sl(ZS_NC ? 3 : 4)], nk, W3[sl(5)], FR[sl(5)], col, pq, nbyz(q), g.nx, op,
                                    dz, rred);
             if (kZsRask)
-                zs_residual_a<T, N, CLZ, ST>(AS[(RS & 1) ^ 1], W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q), g.nx, op, dz,
+                zs_residual_a<T, N, CLZ, ST, TAB>(AS[(RS & 1) ^ 1], W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q), g.nx, op, dz,
                                              rblk);
             else
-                zs_residual<T, N, CLZ, ST>(W3[sl(6)], W3[sl(5)], W3[sl(4)], nr, W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q),
+                zs_residual<T, N, CLZ, ST, TAB>(W3[sl(6)], W3[sl(5)], W3[sl(4)], nr, W4[sl(5)], FB[sl(5)], col, 1 ^ pq, nbyz(q),
                                            g.nx, op, dz, rblk);
             const bool rin = in_xy && (ST || inz(q));  // (the residuals of cells outside the box weigh 0)
             // RX: the group's 2N cells in x order, the low N at t N and the high N at RXH + t N (t = ye G + gx), so
@@ -1230,8 +1244,20 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     PF pb[NPF];
 #pragma unroll
     for (int k = 0; k < NPF; ++k) pb[k].f1 = pb[k].f2 = vz;  // (the halo rows that skip f loads keep zeros)
+    // FACE (cl != 0 levels, whose chunks are short): no step for nothing at the box's z faces.  A chunk at the lower
+    // face starts at pg, past the whole groups of steps in which every stage's plane lies below the box (they move
+    // zeros: the rings and the LDS slots start as zeros), and the steady range [ps, pe] is not rounded to whole
+    // groups: the group that holds ps is generic up to ps - 1 and steady from ps, the one that holds pe is steady up
+    // to pe and generic after it.  A 32-plane POST chunk runs 5 generic steps at either face (the steps with a stage
+    // on or outside the face plane) where it ran 12 and 8.  cl = 0 levels keep whole groups (the bound tests cost
+    // level 0's long steady loop more than its 4 generic steps, see k_zs_split).
+    constexpr bool FACE = !CLZ && !ZS_ALL_GENERIC && !FAI;
+    int pg = zlo;
+    if constexpr (FACE) {
+        if (-z0 - zlo >= UNR) pg = zlo + (-z0 - zlo) / UNR * UNR;
+    }
     if (!PRE) {  // the coarse planes the first fine plane needs
-        const int K = (z0 + zlo) >> 1;
+        const int K = (z0 + (FACE ? pg : zlo)) >> 1;
         for (int k = K - 1; k <= K + 1; ++k) {
             cload(pb[0], k);
             cstore(pb[0], k);
@@ -1239,25 +1265,40 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
         __syncthreads();
     }
 #pragma unroll
-    for (int k = 0; k < PFD; ++k) prefetch(GEN, pb[k], zlo + k);
+    for (int k = 0; k < PFD; ++k) prefetch(GEN, pb[k], (FACE ? pg : zlo) + k);
     // steady steps [ps, pe]: stages inside the box (z0 + p - 5 >= 1, z0 + p < gnz) and the prefetched planes
     // (p + PFD .. p - 4) readable; the chunk's warm-up and drain steps are steady too (their stores are skipped
     // by the uniform chunk test), so a chunk away from the box faces runs no generic step at all (the short
     // chunks of the coarser fused levels were ~45 % generic steps before)
-    int ps = zlo, pe = p_end;
-    ps = ps > 6 - z0 ? ps : 6 - z0;  // PRE's residual plane p - 5 off the z face (steady diagonals have no z face)
-    ps = ps > qlo + 4 ? ps : qlo + 4;
-    pe = pe < gnz - (PRE ? 1 : 2) - z0 ? pe : gnz - (PRE ? 1 : 2) - z0;  // POST: Kn inside the coarse box
-    pe = pe < qhi - PFD ? pe : qhi - PFD;
-    ps += (UNR - (ps - zlo) % UNR) % UNR;  // whole groups of UNR steps in the prologue
-    pe -= (pe - ps + 1) % UNR;             // and in the steady part
-    // no steady part (the epilogue takes all) without a whole group or with odd z0 / Z0 (static parity)
-    // POST with the BQ cache: (z0 + Z0) % 4 == 0 as well (static parity of the coarse plane)
-#ifndef ZS_ALL_GENERIC  // timing experiment: every step generic (the price of the box-face steps)
-#define ZS_ALL_GENERIC 0
-#endif
-    if (ZS_ALL_GENERIC || pe < ps || ((z0 | Z0) & 1) || (!PRE && LINEAR == 1 && ZS_BQ && ((z0 + Z0) & 3))) ps = pe = zlo - 1;
-    int p = zlo;
+    int ps = FACE ? pg : zlo, pe = p_end;
+    if constexpr (!FACE && !FAI) {
+        ps = ps > 6 - z0 ? ps : 6 - z0;  // PRE's residual plane p - 5 off the z face (steady diagonals have no z face)
+        ps = ps > qlo + 4 ? ps : qlo + 4;
+        pe = pe < gnz - (PRE ? 1 : 2) - z0 ? pe : gnz - (PRE ? 1 : 2) - z0;  // POST: Kn inside the coarse box
+        pe = pe < qhi - PFD ? pe : qhi - PFD;
+        ps += (UNR - (ps - zlo) % UNR) % UNR;  // whole groups of UNR steps in the prologue
+        pe -= (pe - ps + 1) % UNR;             // and in the steady part
+        // no steady part (the epilogue takes all) without a whole group or with odd z0 / Z0 (static parity)
+        // POST with the BQ cache: (z0 + Z0) % 4 == 0 as well (static parity of the coarse plane)
+        if (ZS_ALL_GENERIC || pe < ps || ((z0 | Z0) & 1) || (!PRE && LINEAR == 1 && ZS_BQ && ((z0 + Z0) & 3))) ps = pe = zlo - 1;
+    } else {
+        if (!FAI) {  // FACE: POST's last stage's plane p - 4 off the z face
+            const int pz = (PRE ? 6 : 5) - z0;
+            ps = ps > pz ? ps : pz;
+            pe = pe < gnz - (PRE ? 1 : 2) - z0 ? pe : gnz - (PRE ? 1 : 2) - z0;
+        }
+        ps = ps > qlo + 4 ? ps : qlo + 4;
+        pe = pe < qhi - PFD ? pe : qhi - PFD;
+        if (!FACE) {
+            ps += (UNR - (ps - zlo) % UNR) % UNR;
+            pe -= (pe - ps + 1) % UNR;
+        }
+        if (pe < ps || ((z0 | Z0) & 1) || (!PRE && LINEAR == 1 && ZS_BQ && ((z0 + Z0) & 3))) {
+            ps = FACE ? p_end + 1 : zlo - 1;  // (FACE: the prologue's generic steps take all)
+            pe = FACE ? p_end : zlo - 1;
+        }
+    }
+    int p = FACE ? pg : zlo;
     const std::integral_constant<int, -1> RPL;
     // UNR steps from p0 (p0 - zlo a multiple of UNR): ring slot k & 3, buffers k % NPF and (k + PFD) % NPF;
     // steps past plim are skipped (epilogue)
@@ -1269,17 +1310,31 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
                 step(st, std::integral_constant<int, (k & 3)>(), rp, ro, pb[k % NPF], pb[(k + PFD) % NPF], p0 + k);
         });
     };
-    for (; p < ps; p += UNR) group(GEN, RPL, RO0, p, p + UNR);
+    // FACE: the steps pfirst .. plim of the group from p0
+    auto part = [&](auto st, auto rp, auto ro, int p0, int pfirst, int plim) __attribute__((always_inline)) {
+        zs_unroll<UNR>([&](auto kk) __attribute__((always_inline)) {
+            constexpr int k = decltype(kk)::value;
+            if (p0 + k >= pfirst && p0 + k <= plim)
+                step(st, std::integral_constant<int, (k & 3)>(), rp, ro, pb[k % NPF], pb[(k + PFD) % NPF], p0 + k);
+        });
+    };
+    if constexpr (FACE) {
+        for (; p + UNR <= ps; p += UNR) group(GEN, RPL, RO0, p, p + UNR);
+        if (p < ps) part(GEN, RPL, RO0, p, p, ps - 1);  // (p stays: the start of the group that holds ps)
+    } else {
+        for (; p < ps; p += UNR) group(GEN, RPL, RO0, p, p + UNR);
+    }
     auto steady = [&](auto rp, auto ro) __attribute__((always_inline)) {
         if constexpr (!PRE && LINEAR == 1 && ZS_BQ) {
-            if (p <= pe) {  // the first steady step (even, K & 1 == 0) reads coarse planes K and K - 1
+            if (FACE ? ps <= pe : p <= pe) {  // the first steady step (even, K & 1 == 0) reads coarse planes K and K - 1
                 const int K = (z0 + p) >> 1;
                 bq_fill(rp, BQ[0], K);
-                bq_fill(rp, BQ[1], K - 1);
+                // (FACE: the steady steps may begin at the group's third or fourth step, which read K + 1)
+                bq_fill(rp, BQ[1], FACE && ps - p >= 2 ? K + 1 : K - 1);
             }
         }
         for (; p <= pe; p += UNR) {
-#ifdef ZS_STAMP  // timing experiment (wrong results): POST's wall clock every 16 steps into R (level 1's f)
+#ifdef ZS_STAMP // timing experiment (wrong results): POST's wall clock every 16 steps into R (level 1's f)
             if (!PRE && tid == 0 && ((p - zlo) & 15) == 0 && (p - zlo) / 16 < 32) {
                 const unsigned long long w = wall_clock64();
                 float* out = reinterpret_cast<float*>(R) + 64 * (int)blockIdx.x + 2 * ((p - zlo) / 16);
@@ -1287,7 +1342,13 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
                 out[1] = __uint_as_float((unsigned)(w >> 32));
             }
 #endif
-            group(STY, rp, ro, p, p + UNR);
+            // (FACE: every steady step behind its bound tests.  A second copy of the group without them for the whole
+            // groups, chosen inside this loop, made the fp32 cl != 0 instantiations spill (POST 168 VGPRs + 34 spilled);
+            // as loops of their own, head / whole groups / tail, the 256^3 POST measured 63.3 against 62.3 us)
+            if constexpr (FACE)
+                part(STY, rp, ro, p, ps, pe);
+            else
+                group(STY, rp, ro, p, p + UNR);
         }
     };
     if constexpr (S::PS) {  // wave-uniform: one copy of the steady loop per row parity
@@ -1298,7 +1359,11 @@ __attribute__((amdgpu_waves_per_eu(1, PRE ? ZS_WPE_PRE : ZS_WPE_POST))) void k_z
     } else {
         steady(RPL, RO0);
     }
-    for (; p <= p_end; p += UNR) group(GEN, RPL, RO0, p, p_end);
+    if constexpr (FACE) {  // from pe + 1, in the group that holds it
+        for (p = pg + (pe + 1 - pg) / UNR * UNR; p <= p_end; p += UNR) part(GEN, RPL, RO0, p, pe + 1, p_end);
+    } else {
+        for (; p <= p_end; p += UNR) group(GEN, RPL, RO0, p, p_end);
+    }
     if constexpr (ERR && !PRE) block_partial_t<NTL>(err + err1, partials);  // (PRE: ERR is ZSRC, no partials)
 }
 
