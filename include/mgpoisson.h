@@ -230,6 +230,50 @@ int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnor
  * mgp_refine_remove_mean. */
 int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
 
+/* Full multigrid start (FMG, nested iteration; build-defined, no reference counterpart).  mgp_fmg reads level 0's f,
+ * ignores the stored psi, and
+ *   1. restricts f down the hierarchy (f of l+1 = R f of l, l = 0 .. last-1);
+ *   2. zeroes the coarsest u and runs the coarse solve (mgp_coarse_solve's sweeps);
+ *   3. for l = last-1 .. 1: u of l = P3 u of l+1; u of l+1 = 0 (under both coarse_init values); cycles_per_level >= 1
+ *      cycles of the context's kind (V / F) from level l with h = 2^l / n[0], on the engines the cycle runs there;
+ *   4. the same onto level 0: psi = P3 u of 1, u of 1 = 0;
+ *   5. final_cycles >= 0 ordinary outer iterations (mgp_cycles' path: graph replay, fused err, psiOld), errs
+ *      [final_cycles] as mgp_cycles returns them (may be NULL).
+ * One host synchronisation, at the end.  A cycle from level l writes no f at level l or above, so every level's
+ * restricted f is intact when the ascent arrives there.  With final_cycles = 0, psiOld and the metrics are invalid
+ * until the next outer iteration (mgp_metrics, MGP_FIELD_PSI_OLD / _ERROR: MGP_ERR_STATE, as after mgp_remove_mean).
+ *
+ * Arithmetic: every expression in the field's real type T, each operation rounded, no contraction.
+ * R is the context's `restriction` applied to f itself: the 2^d average in reduceResidual's term order
+ *     R = 1/8 (((((((f000 + f100) + f010) + f110) + f001) + f101) + f011) + f111)      (x fastest; 2D: 1/4 of four)
+ * or the full weighting with face weight 3 - c_{l+1} (the restriction mgp_residual_restrict applies to the residual).
+ * P3 REPLACES every cell of u (it does not add).  It is separable, one pass per active axis in the order x, y, z, each
+ * on the result of the pass before (2D: z is not touched).  Along one axis the coarse line A[0 .. m) is extended by two
+ * ghosts per side, mc = -(T)c_{l+1} (c: the boundary coefficient of coarse_bc, mgp_level_info):
+ *     E[-1] = mc E[0],  E[-2] = mc E[1],  E[m] = mc E[m-1],  E[m+1] = mc E[m-2]
+ *     (m = 1: E[-1] = E[1] = mc A[0], E[-2] = E[2] = mc (mc A[0])).
+ * Each ghost is one multiplication, always performed; the ghost lines of the y and z passes are mc times the already
+ * x- (x, y-) interpolated in-box line.  The two children of coarse cell I are
+ *     child 2I     = ((wp E[I] + wn E[I-1]) + wq E[I+1]) + wr E[I-2]
+ *     child 2I + 1 = ((wp E[I] + wn E[I+1]) + wq E[I-1]) + wr E[I+2]
+ * with wp = 105/128, wn = 35/128, wq = -7/128, wr = -5/128: the cubic Lagrange weights at -+1/4 of a coarse cell.
+ * Under MGP_BC_FACE / _NEUMANN / _CONSISTENT one cycle per level and one final cycle leave an algebraic error below
+ * the discretisation error on smooth problems; under MGP_BC_ZERO the coarse operators are inconsistent with level 0
+ * (the known mismatch) and no accuracy is claimed.
+ *
+ * The pieces (for tests and hybrid drivers) synchronise like mgp_residual_restrict: mgp_fmg_restrict_rhs writes f of
+ * level + 1 from f of level; mgp_fmg_prolong writes u of level from u of level + 1 (on level 0 psiOld and the metrics
+ * become invalid).  Under mgp_set_debug(1) every piece's output is checked and named like the cycle's phases.
+ *
+ * Refused: NULL context, bad level, cycles_per_level < 1, final_cycles < 0, an MGP_ARITH_DOUBLE context: MGP_ERR_ARG;
+ * world > 1, loopback and group ranks, MGP_TRANSPORT=rccl ("single-GPU contexts only"), active refinement, and (mgp_fmg)
+ * a coarse hand-off: MGP_ERR_STATE.  Limits: no slab or group contexts (the cubic stencil needs a second coarse ghost
+ * plane), no batches, no mixed-precision refinement, the ascent is not captured in a hipGraph (only the final outer
+ * iterations replay one), and the ascent runs the levels of the LDS coarse engine with its launches, not inside it. */
+int         mgp_fmg_restrict_rhs(mgp_ctx* c, int level);   /* f of level+1 = R f of level */
+int         mgp_fmg_prolong(mgp_ctx* c, int level);        /* u of level = P3 u of level+1 (replaces u) */
+int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs);
+
 /* The reference's Krylov cross-check (test/converge-multigrid-vs-krylov.lua:38-69, solver.conjgrad) on
  * the device, as an independent second oracle for the converged multigrid answer: matrix-free
  * conjugate gradients on the finest level's operator (same 5-/7-point stencil and box boundary) from

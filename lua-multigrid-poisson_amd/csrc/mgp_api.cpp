@@ -2740,14 +2740,9 @@ static int enqueue_cycles(mgp_ctx* c, int32_t k)
     return rc;
 }
 
-int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
+// the errs of the k outer iterations enqueue_cycles ran, after the stream's synchronisation (errs may be NULL)
+static int read_errs(mgp_ctx* c, int32_t k, double* errs)
 {
-    if (!c || k < 0) return MGP_ERR_ARG;
-    if (c->refining()) return refine_refuses(c, "mgp_cycles");
-    TRY(debug_reset(c));
-    TRY(enqueue_cycles(c, k));
-    TRY(sync_and_check(c));
-    TRY(debug_verdict(c));
     if (errs) {
         if (!c->o.err_mode) {
             for (int i = 0; i < k; ++i) errs[i] = NAN;
@@ -2762,6 +2757,17 @@ int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
         }
     }
     return MGP_OK;
+}
+
+int mgp_cycles(mgp_ctx* c, int32_t k, double* errs)
+{
+    if (!c || k < 0) return MGP_ERR_ARG;
+    if (c->refining()) return refine_refuses(c, "mgp_cycles");
+    TRY(debug_reset(c));
+    TRY(enqueue_cycles(c, k));
+    TRY(sync_and_check(c));
+    TRY(debug_verdict(c));
+    return read_errs(c, k, errs);
 }
 
 int mgp_cycle(mgp_ctx* c, double* err_out)
@@ -2873,6 +2879,109 @@ int mgp_coarse_solve(mgp_ctx* c)
     const int l = (int)c->lev.size() - 1;
     TRY(coarse_solve_at(c, l, level_h(c, l)));
     return sync_and_check(c);
+}
+
+// ---- full multigrid start (mgp_fmg.hip's passes; the header has the definition) ----
+
+static int fmg_refuses(mgp_ctx* c, const char* what)
+{
+    if (c->rk == mgp::kRealF32D)
+        return c->fail(MGP_ERR_ARG, "%s: the passes evaluate in the real type; arith = MGP_ARITH_DOUBLE is not supported",
+                       what);
+    if (c->multi() || c->lb) return c->fail(MGP_ERR_STATE, "%s: single-GPU contexts only", what);
+    if (c->refining()) return refine_refuses(c, what);
+    return MGP_OK;
+}
+
+// f of level l + 1 = R f of level l (the context's restriction on the stored field)
+static int fmg_restrict_rhs(mgp_ctx* c, int l)
+{
+    Level& L = c->lev[l];
+    Level& C = c->lev[l + 1];
+    int64_t zc = 0;
+    const Geo gc = coarse_view(L, C, &zc);
+    char* R = c->ui(C, C.f) + (size_t)(zc * C.g.P) * c->rb;
+    if (c->o.restriction == MGP_RESTRICT_FULL_WEIGHTING)
+        HIP_TRY(c, mgp::launch_fw_restrict(c->rk, c->o.dim, c->ui(L, L.f), R, L.g, gc,
+                                           coarse_coef(c->o.coarse_bc, l + 1), c->s));
+    else
+        HIP_TRY(c, mgp::launch_restrict_field(c->rb, c->o.dim, c->ui(L, L.f), R, L.g, gc, c->s));
+    C.fghost_ok = !C.p.dist;
+    return debug_check(c, l + 1, "the right-hand-side restriction (FMG: f of the coarse level)", true);
+}
+
+// u of level l = P3 u of level l + 1: every cell is written, so a pending zero of level l needs no memset
+static int fmg_prolong(mgp_ctx* c, int l)
+{
+    Level& L = c->lev[l];
+    Level& C = c->lev[l + 1];
+    TRY(materialize_zero(c, C));
+    int64_t zc = 0;
+    const Geo gc = coarse_view(L, C, &zc);
+    char* V = c->ui(C, C.u) + (size_t)(zc * C.g.P) * c->rb;
+    HIP_TRY(c, mgp::launch_fmg_prolong(c->rb, c->o.dim, c->ui(L, L.u), V, L.g, gc, coarse_coef(c->o.coarse_bc, l + 1),
+                                       c->s));
+    L.zero_pending = false;
+    L.ghost_ok = !L.p.dist;
+    L.ghost_zero = false;
+    if (l == 0) c->metrics_old = nullptr;  // psiOld and the metrics describe an iterate that is gone
+    return debug_check(c, l, "the cubic prolongation (FMG: u)");
+}
+
+int mgp_fmg_restrict_rhs(mgp_ctx* c, int level)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (level < 0 || level + 1 >= (int)c->lev.size()) return c->fail(MGP_ERR_ARG, "mgp_fmg_restrict_rhs: bad level %d", level);
+    TRY(fmg_refuses(c, "mgp_fmg_restrict_rhs"));
+    TRY(debug_reset(c));
+    c->dbg_cycle = 0;
+    TRY(fmg_restrict_rhs(c, level));
+    TRY(sync_and_check(c));
+    return debug_verdict(c);
+}
+
+int mgp_fmg_prolong(mgp_ctx* c, int level)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (level < 0 || level + 1 >= (int)c->lev.size()) return c->fail(MGP_ERR_ARG, "mgp_fmg_prolong: bad level %d", level);
+    TRY(fmg_refuses(c, "mgp_fmg_prolong"));
+    TRY(debug_reset(c));
+    c->dbg_cycle = 0;
+    TRY(fmg_prolong(c, level));
+    TRY(sync_and_check(c));
+    return debug_verdict(c);
+}
+
+int mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (cycles_per_level < 1 || final_cycles < 0)
+        return c->fail(MGP_ERR_ARG, "mgp_fmg: cycles_per_level >= 1 and final_cycles >= 0");
+    TRY(fmg_refuses(c, "mgp_fmg"));
+    if (c->handoff_fn) return c->fail(MGP_ERR_STATE, "mgp_fmg: a coarse hand-off is set (mgp_set_coarse_handoff)");
+    const int last = (int)c->lev.size() - 1;
+    const bool fcycle = c->o.cycle == MGP_CYCLE_F;
+    TRY(debug_reset(c));
+    c->dbg_cycle = 0;
+    for (int l = 0; l < last; ++l) TRY(fmg_restrict_rhs(c, l));
+    TRY(zero_level(c, c->lev[last]));
+    TRY(coarse_solve_at(c, last, level_h(c, last)));
+    TRY(debug_check(c, last, "the coarse solve (FMG)"));
+    c->metrics_old = nullptr;  // the stored psi is replaced (or, on a one-level box, solved again from zero)
+    for (int l = last - 1; l >= 0; --l) {
+        TRY(fmg_prolong(c, l));
+        // The level below starts the cycles of level l as a zero correction guess, under MGP_COARSE_WARM too.  A real
+        // zero: a lazy one is a host flag for the cycle's first reader of that level, and the readers here (the coarse
+        // engine from its first level, a replayed graph of level 0's outer iterations) are not all such readers.
+        TRY(zero_level(c, c->lev[l + 1]));
+        TRY(materialize_zero(c, c->lev[l + 1]));
+        if (l == 0) break;
+        for (int k = 0; k < cycles_per_level; ++k) TRY(cycle_rec(c, l, level_h(c, l), fcycle));
+    }
+    TRY(enqueue_cycles(c, final_cycles));
+    TRY(sync_and_check(c));
+    TRY(debug_verdict(c));
+    return read_errs(c, final_cycles, errs);
 }
 
 int mgp_sync(mgp_ctx* c) { return c ? sync_and_check(c) : MGP_ERR_ARG; }

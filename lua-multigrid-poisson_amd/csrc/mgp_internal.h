@@ -1,7 +1,7 @@
 // mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4 kernel units:
 // mgp_kernels.hip (one launch per piece; k_zs's stage-split variants and the 2D k_ys), mgp_zs.hip / mgp_zs_f64.hip (k_zs, the fused
 // phases' planning and dispatch), mgp_tail.hip (coarse tail), mgp_blk.hip / mgp_blk2.hip (tiled phases), mgp_gslex.hip,
-// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip.  The last block holds what the kernel units
+// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip, mgp_fmg.hip.  The last block holds what the kernel units
 // call in each other.  Not part of the public ABI (include/mgpoisson.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,6 +147,13 @@ hipError_t launch_resfw(int rb, int dim, const void* u, const void* f, void* R, 
 // every red cell without reading it).
 hipError_t launch_prolong_correct(int rb, int dim, int linear, void* u, const void* V, Geo g, Geo gc, double clc,
                                   hipStream_t s, bool black_only = false);
+// The passes of the full multigrid start (mgp_fmg.hip; rb = 4 / 8, one rank's whole box: z0 = 0, every plane local).
+// launch_restrict_field: R (coarse packed, Geo gc) = the 2^d average of the stored field f in reduceResidual's term
+// order (the full weighting of a stored field is launch_fw_restrict).  launch_fmg_prolong: every cell of u = P3 V, the
+// separable cubic interpolation (x, y, z passes; ghosts -clc times the mirrored in-box line; mgp_fmg.hip's header has
+// the expressions).  V's and u's ghost planes are not read.
+hipError_t launch_restrict_field(int rb, int dim, const void* f, void* R, Geo g, Geo gc, hipStream_t s);
+hipError_t launch_fmg_prolong(int rb, int dim, void* u, const void* V, Geo g, Geo gc, double clc, hipStream_t s);
 // Deterministic two-pass fp64 sum of (a - b)^2 over n elements into *out (ctr != nullptr: into
 // out[*ctr], then ++*ctr on the device).
 // lev (here and in launch_metrics): a and b are whole levels of that layout, n = lev->P * planes.  The sum then runs

@@ -101,6 +101,9 @@ int         mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* fro
 int         mgp_set_debug(mgp_ctx* c, int mode);
 int         mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm);
 int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
+int         mgp_fmg_restrict_rhs(mgp_ctx* c, int level);
+int         mgp_fmg_prolong(mgp_ctx* c, int level);
+int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs);
 int         mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean);
 int         mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean);
 int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
@@ -504,6 +507,28 @@ function MultigridHIP:solve()
 	end
 	if neumann then self:removeMean('psi') end
 end
+
+-- full multigrid start (this build's addition, mgp_fmg): psi from f alone (f restricted down the hierarchy, the
+-- coarsest level solved, per level the cubic prolongation and `cycles` cycles), then `final` outer iterations.
+-- Returns the last one's err (nan for final = 0).  boundary = 'neumann': f's mean is removed first, psi's afterwards.
+function MultigridHIP:fmg(cycles, final)
+	if rawget(self, 'group') then error('fmg: single-GPU solvers only (ngpu > 1 runs mgp_group_*)', 2) end
+	if rawget(self, 'mixed') then error("fmg: real = 'mixed' is not supported", 2) end
+	self:applyKnobs()
+	cycles, final = cycles or 1, final or 1
+	local errs = ffi.new('double[?]', math.max(final, 1))
+	local neumann = rawget(self, 'boundary') == 'neumann'
+	if neumann then self:removeMean('f') end
+	check(lib.mgp_fmg(self.ctx, cycles, final, errs), self.ctx)
+	if neumann then self:removeMean('psi') end
+	local err = final > 0 and errs[final - 1] or 0 / 0
+	if self.debug then print('err', err) end
+	return err
+end
+
+-- the pieces of the full multigrid start: f of level + 1 = R f of level; u of level = P3 u of level + 1
+function MultigridHIP:fmgRestrictRhs(level) check(lib.mgp_fmg_restrict_rhs(self.ctx, level), self.ctx) end
+function MultigridHIP:fmgProlong(level) check(lib.mgp_fmg_prolong(self.ctx, level), self.ctx) end
 
 -- cpu-raw.lua:239-258 / gpu.lua:348-373: two outer iterations
 function MultigridHIP:run()

@@ -118,6 +118,9 @@ SIGNATURES = {
     "mgp_residual_restrict": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mgp_prolong_correct": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mgp_coarse_solve": (ctypes.c_int, [_vp]),
+    "mgp_fmg_restrict_rhs": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "mgp_fmg_prolong": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "mgp_fmg": (ctypes.c_int, [_vp, _i32, _i32, _P(_dbl)]),
     "mgp_sync": (ctypes.c_int, [_vp]),
     "mgp_metrics": (ctypes.c_int, [_vp, _P(_dbl), _P(_i64), _P(_dbl)]),
     "mgp_set_coarse_level": (ctypes.c_int, [_vp, _i64]),

@@ -209,6 +209,22 @@ class Context:
     def coarse_solve(self):
         self._chk(L.lib.mgp_coarse_solve(self._h))
 
+    # -- full multigrid start --
+    def fmg(self, cycles: int = 1, final: int = 1) -> np.ndarray:
+        """mgp_fmg: psi from level 0's f alone (f restricted down, the coarsest level solved, then per level the cubic
+        prolongation and `cycles` cycles), then `final` outer iterations; returns their errs."""
+        errs = np.zeros(max(int(final), 0), dtype=np.float64)
+        self._chk(L.lib.mgp_fmg(self._h, int(cycles), int(final), errs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return errs
+
+    def fmg_restrict_rhs(self, level):
+        """f of level + 1 = the context's restriction of f of level."""
+        self._chk(L.lib.mgp_fmg_restrict_rhs(self._h, int(level)))
+
+    def fmg_prolong(self, level):
+        """u of level = the cubic prolongation of u of level + 1 (replaces u)."""
+        self._chk(L.lib.mgp_fmg_prolong(self._h, int(level)))
+
     def set_coarse_level(self, size: int):
         """Levels of nx <= size run in the one-launch LDS coarse engine (cpuDepth, cpu-gpu.lua:61)."""
         self._chk(L.lib.mgp_set_coarse_level(self._h, int(size)))

@@ -272,6 +272,25 @@ class MultigridHIP(_RawFields):
         if self.boundary == "neumann":
             self.remove_mean("psi")
 
+    def fmg(self, cycles=1, final=1) -> float:
+        """Full multigrid start (this build's addition, mgp_fmg): psi from f alone — f restricted down the hierarchy,
+        the coarsest level solved, then per level the cubic prolongation and ``cycles`` cycles — followed by ``final``
+        outer iterations; returns the last one's err (NaN with ``final`` = 0).  boundary='neumann': f's mean is
+        removed first and psi's afterwards, as in ``solve()``."""
+        if self.mixed:
+            raise ValueError("fmg: real='mixed' is not supported (the full multigrid start runs in the context's real "
+                             "type; use real='float' or 'double')")
+        self._ensure_ctx()
+        if self.boundary == "neumann":
+            self.remove_mean("f")
+        errs = self._ctx.fmg(cycles, final)
+        if self.boundary == "neumann":
+            self.remove_mean("psi")
+        err = float(errs[-1]) if len(errs) else float("nan")
+        if self.debug:
+            print("err", err)
+        return err
+
     def twoGrid(self, h, u, f):
         """cpu.lua:70 twoGrid(h, u, f): u updated in place.  u / f are (L, L[, L]) host arrays, or
         cpu.lua-style 1-based-indexed nested lists u[i][j] (x = i), whose rows are updated in place."""
