@@ -268,8 +268,9 @@ int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
  * Refused: NULL context, bad level, cycles_per_level < 1, final_cycles < 0, an MGP_ARITH_DOUBLE context: MGP_ERR_ARG;
  * world > 1, loopback and group ranks, MGP_TRANSPORT=rccl ("single-GPU contexts only"), active refinement, and (mgp_fmg)
  * a coarse hand-off: MGP_ERR_STATE.  Limits: no slab or group contexts (the cubic stencil needs a second coarse ghost
- * plane), no batches, no mixed-precision refinement, the ascent is not captured in a hipGraph (only the final outer
- * iterations replay one), and the ascent runs the levels of the LDS coarse engine with its launches, not inside it. */
+ * plane), no mixed-precision refinement, the ascent is not captured in a hipGraph (only the final outer iterations
+ * replay one), and the ascent runs the levels of the LDS coarse engine with its launches, not inside it (a batch,
+ * mgp_batch_fmg, does both: one captured ascent whose LDS levels are one launch). */
 int         mgp_fmg_restrict_rhs(mgp_ctx* c, int level);   /* f of level+1 = R f of level */
 int         mgp_fmg_prolong(mgp_ctx* c, int level);        /* u of level = P3 u of level+1 (replaces u) */
 int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs);
@@ -410,6 +411,37 @@ int         mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm);
 int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
 /* Kernel launches (graph nodes included) one cycle of the last mgp_batch_cycles / mgp_batch_solve enqueued. */
 int         mgp_batch_launches(const mgp_batch* b, int64_t* per_cycle);
+/* Full multigrid start of EVERY member: per member mgp_batch_fmg is mgp_fmg's definition above (steps 1-5) with the same
+ * arithmetic (every operation rounded in the real type, no contraction; R the 2^d average in reduceResidual's term order;
+ * P3 with the ghost rule mc = -(T)c_{l+1}, the weights 105, 35, -7, -5 over 128 and the pass order x, y, z; the level
+ * below set to a real zero after each P3 under both coarse_init values), so a member's u and f on every level equal,
+ * bit for bit, what mgp_fmg leaves on an ordinary context with that member's f.  The stored psi is ignored: no u of any
+ * level is read before the call has written it.  All members are armed as mgp_batch_cycles arms them (a stop state
+ * left by mgp_batch_solve excludes nobody); errs (may be NULL): final_cycles * B doubles, errs[it * B + m] (NaN with
+ * err_mode 0).  One host synchronisation, at the end, in every call after the first use of a cycles_per_level value;
+ * that first use also builds and uploads the LDS program and captures the ascent's graph (blocking copies, one more
+ * synchronisation).
+ * Engines: the restrictions of f down to the first LDS level T run one launch per level; the levels from T down are ONE
+ * launch with one workgroup per member (the restriction of f from T, the coarse solve, every P3 and every per-level
+ * cycle, all in LDS; only level T's f is read from memory); the levels above run one launch per piece, the P3 onto a
+ * level whose coarse rows hold 16 bytes of reals in mgp_fmg's marching vector form over all members.  The ascent is one
+ * captured graph (a single chain, kept for the last cycles_per_level; MGP_GRAPH=0: eager launches, identical bits);
+ * the final iterations replay the cycle's graph.  The LDS program's length grows with cycles_per_level; it lives in a
+ * device array of its own, built on the first use of a cycles_per_level value and kept for the last one.  A program of
+ * more than 4096 ops (cycles_per_level <= 2 never is) runs the LDS levels' ascent per piece as well, with identical
+ * bits.  MGP_TAIL=0: every level per piece.
+ * After final_cycles = 0 (and after mgp_batch_fmg_prolong onto level 0) psiOld describes an iterate that is gone: a
+ * read of MGP_FIELD_PSI_OLD returns MGP_ERR_STATE until the next outer iteration, as on the ordinary context.
+ * The two pieces run on every member (stopped ones included) and synchronise like mgp_batch_remove_mean.
+ * mgp_batch_fmg_launches: the kernel launches (graph nodes included) of the last call's ascent, without the final outer
+ * iterations; it does not depend on B.
+ * MGP_ERR_ARG: NULL batch, a level outside [0, levels - 2], cycles_per_level < 1, final_cycles < 0.  Out of scope: slab
+ * and group contexts, mixed-precision refinement, the full weighting (batches refuse it), a per-member stop inside the
+ * ascent.  Measured (tools/batch_fmg_time.py, profiles/batch_fmg_time.json): README "Many small boxes at once". */
+int         mgp_batch_fmg_restrict_rhs(mgp_batch* b, int level);  /* every member: f of level+1 = R f of level */
+int         mgp_batch_fmg_prolong(mgp_batch* b, int level);       /* every member: u of level = P3 u of level+1 (replaces u) */
+int         mgp_batch_fmg(mgp_batch* b, int32_t cycles_per_level, int32_t final_cycles, double* errs);
+int         mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent);
 
 /* The reference's debugging check (MultigridCPURaw.debugging / MultigridGPU.debugging: show / showAndCheck after
  * every sweep and piece of twoGrid, error "found a nan" on a non-finite cell; cpu-raw.lua:126-140,

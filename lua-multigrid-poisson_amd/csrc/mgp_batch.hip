@@ -14,7 +14,12 @@
 // LDS) run as ONE launch with one workgroup per member, executing the op program of the coarse sub-cycle (the one
 // the ordinary context's tail executes) from LDS; the levels above run one launch per piece (half-sweep, residual
 // + restriction, prolongation + correction).  Both engines execute the same per-piece device functions.
-#include "mgp_device.h"
+//
+// mgp_batch_fmg (the full multigrid start per member, mgp_fmg's definition): the levels from T down are one launch of the
+// LDS engine as well (k_batch_tail<.., FMG = true>: its op program restricts f, solves the coarsest level and runs every
+// cubic prolongation and per-level cycle up to level T), the levels above one launch per piece (k_batch_restrict_field;
+// the marching vector P3 of mgp_fmg.hip over all members, or k_batch_fmg_prolong), all captured as one graph.
+#include "mgp_fmg_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -164,6 +169,75 @@ __device__ __forceinline__ void prolong_part(T* u, const T* V, const BLev<T, DIM
     }
 }
 
+// The two passes of the full multigrid start (mgp_batch_fmg; the definitions are mgp_fmg's in the header).
+
+// R = the 2^d average of the stored field f in reduceResidual's term order (x fastest): a work item per coarse slot
+template <typename T, int DIM>
+__device__ __forceinline__ void restrict_field_part(const T* f, T* R, const MGeo& g, const MGeo& gc, int tid, int nt)
+{
+    const int n = gc.nz * gc.P;
+    for (int q = tid; q < n; q += nt) {
+        int I, J, K;
+        if (!slot_of(q, gc, I, J, K)) continue;
+        T s = (T)0;
+#pragma unroll
+        for (int d = 0; d < (1 << DIM); ++d) {
+            const T v = f[pslot(g, 2 * I + (d & 1), 2 * J + ((d >> 1) & 1), DIM == 3 ? 2 * K + (d >> 2) : 0)];
+            s = d == 0 ? v : s + v;
+        }
+        R[q] = (DIM == 2 ? (T)0.25 : (T)0.125) * s;
+    }
+}
+
+// u = P3 V, mc = -(T)c of the coarse level: a work item per fine slot, the expressions of k_fmg_prolong_s (mgp_fmg.hip).
+// In 3D the four z terms are computed one after the other and enter the z pass's sum as they come, ((wp z0 + wn z1) +
+// wq z2) + wr z3 with every product and sum rounded as cub rounds them: 16 coarse samples are live, not 64, so the LDS
+// ascent keeps the cycle's 1024-thread workgroup without spilling.
+template <typename T, int DIM>
+__device__ __forceinline__ void fmg_prolong_part(T* u, const T* V, const MGeo& g, const MGeo& gc, T mc, int tid, int nt)
+{
+    const int n = g.nz * g.P;
+    for (int s = tid; s < n; s += nt) {
+        int i, j, k;
+        if (!slot_of(s, g, i, j, k)) continue;
+        const int I = i >> 1, J = j >> 1, K = DIM == 3 ? (k >> 1) : 0;
+        const int sx = (i & 1) ? 1 : -1, sy = (j & 1) ? 1 : -1, sz = (k & 1) ? 1 : -1;
+        const int mz = DIM == 3 ? gc.nz : 1;
+        T acc = (T)0;
+#pragma unroll 1
+        for (int tz = 0; tz < (DIM == 3 ? 4 : 1); ++tz) {
+            const int dz = tz == 0 ? 0 : (tz == 1 ? sz : (tz == 2 ? -sz : 2 * sz));
+            int nz_ = 0;
+            const int Kq = DIM == 3 ? ext_src(K + dz, mz, nz_) : 0;
+            T yt[4];
+#pragma unroll
+            for (int ty = 0; ty < 4; ++ty) {
+                const int dy = ty == 0 ? 0 : (ty == 1 ? sy : (ty == 2 ? -sy : 2 * sy));
+                int ny_;
+                const int Jq = ext_src(J + dy, gc.ny, ny_);
+                T xt[4];
+#pragma unroll
+                for (int tx = 0; tx < 4; ++tx) {
+                    const int dx = tx == 0 ? 0 : (tx == 1 ? sx : (tx == 2 ? -sx : 2 * sx));
+                    int nx_;
+                    const int Iq = ext_src(I + dx, gc.nx, nx_);
+                    xt[tx] = ext_scale(V[pslot(gc, Iq, Jq, Kq)], nx_, mc);
+                }
+                yt[ty] = ext_scale(cub(xt[0], xt[1], xt[2], xt[3]), ny_, mc);
+            }
+            const T zt = ext_scale(cub(yt[0], yt[1], yt[2], yt[3]), nz_, mc);
+            if (DIM == 3) {
+                const T w = tz == 0 ? W3<T>::wp : (tz == 1 ? W3<T>::wn : (tz == 2 ? W3<T>::wq : W3<T>::wr));
+                const T p = w * zt;
+                acc = tz == 0 ? p : acc + p;
+            } else {
+                acc = zt;
+            }
+        }
+        u[s] = acc;
+    }
+}
+
 // ---- one launch per piece: workgroups [m * nb, (m + 1) * nb) work on member m -----------------------------------
 
 #define BATCH_MEMBER()                                                          \
@@ -196,6 +270,30 @@ __global__ __launch_bounds__(kBlock) void k_batch_prolong(T* u, const T* V, BLev
 {
     BATCH_MEMBER();
     prolong_part<T, DIM>(u + (int64_t)m * L.slots, V + (int64_t)m * (gc.nz * gc.P), L, gc, clc, linear, tid, nt);
+}
+
+// The full multigrid start's passes per piece (active == nullptr: every member, the ABI's two pieces).  The P3 onto a
+// level whose coarse rows hold 16 bytes of reals runs mgp_fmg.hip's marching vector form (launch_fmg_prolong_batch).
+template <typename T, int DIM>
+__global__ __launch_bounds__(kBlock) void k_batch_restrict_field(const T* f, T* R, Geo lg, Geo lgc, int nb,
+                                                                 const int* __restrict__ active)
+{
+    const int m = (int)(blockIdx.x / (unsigned)nb);
+    if (active && !active[m]) return;
+    const int tid = (int)(blockIdx.x - (unsigned)m * nb) * kBlock + (int)threadIdx.x, nt = nb * kBlock;
+    const MGeo g = mgeo(lg), gc = mgeo(lgc);
+    restrict_field_part<T, DIM>(f + (int64_t)m * (g.nz * g.P), R + (int64_t)m * (gc.nz * gc.P), g, gc, tid, nt);
+}
+
+template <typename T, int DIM>
+__global__ __launch_bounds__(kBlock) void k_batch_fmg_prolong(T* u, const T* V, Geo lg, Geo lgc, T mc, int nb,
+                                                              const int* __restrict__ active)
+{
+    const int m = (int)(blockIdx.x / (unsigned)nb);
+    if (active && !active[m]) return;
+    const int tid = (int)(blockIdx.x - (unsigned)m * nb) * kBlock + (int)threadIdx.x, nt = nb * kBlock;
+    const MGeo g = mgeo(lg), gc = mgeo(lgc);
+    fmg_prolong_part<T, DIM>(u + (int64_t)m * (g.nz * g.P), V + (int64_t)m * (gc.nz * gc.P), g, gc, mc, tid, nt);
 }
 
 // dst = src (src == nullptr: +0) over a member's slots: the psiOld snapshot, a fresh coarse guess, a Jacobi level's
@@ -418,11 +516,24 @@ struct BTail {
     T* u[kTailMaxLevels];            // global fields of all members (member stride = slots)
     T* f[kTailMaxLevels];
     uint32_t ops[2][kTailMaxOps];    // TailOp | level << 4 | arg << 8, levels relative to the first
+    const uint32_t* fprog;           // the LDS ascent's program (mgp_batch_fmg; a device array of its own length)
+    int nfprog;
 };
 
 // zero_first: the first level's u is a fresh zero guess (never read from memory)
+// FMG: the LDS ascent of mgp_batch_fmg in place of a sub-cycle: the program sp->fprog (TAIL_FMG_RESTRICT down from the
+// first level's f, the coarsest level zeroed and solved, then per level TAIL_FMG_PROLONG, TAIL_ZERO of the level below
+// and the cycles' own ops).  Only the first level's f is loaded: every u is written before it is read (slots that hold
+// no cell start as 0).  fcycle and zero_first are not read.  It runs with the cycle's workgroup size except in 3D fp64,
+// where the residual + restriction already fills a 1024-thread workgroup's 128 registers (the cycle's instantiation
+// spills there) and the ascent's further ops would spill more: at most 512 threads (256 registers), no scratch.
 template <typename T, int DIM>
-__global__ __launch_bounds__(1024) void k_batch_tail(const BTail<T, DIM>* __restrict__ sp, int fcycle, int zero_first,
+constexpr int tail_max_threads(bool fmg)
+{
+    return fmg && DIM == 3 && sizeof(T) == 8 ? 512 : 1024;
+}
+template <typename T, int DIM, bool FMG>
+__global__ __launch_bounds__((tail_max_threads<T, DIM>(FMG))) void k_batch_tail(const BTail<T, DIM>* __restrict__ sp, int fcycle, int zero_first,
                                                      const int* __restrict__ active)
 {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -434,9 +545,15 @@ __global__ __launch_bounds__(1024) void k_batch_tail(const BTail<T, DIM>* __rest
     for (int l = 0; l < t.nlev; ++l) {
         const int64_t n = t.lev[l].slots;
         T* const lu = lds + t.off[l];
-        const bool zero = l == 0 ? zero_first != 0 : !t.warm;
-        const T* const gu = t.u[l] + (int64_t)m * n;
-        for (int64_t s = tid; s < n; s += nt) lu[s] = zero ? (T)0 : gu[s];
+        if constexpr (FMG) {
+            for (int64_t s = tid; s < n; s += nt) lu[s] = (T)0;
+            if (t.jacobi)
+                for (int64_t s = tid; s < n; s += nt) lu[2 * n + s] = (T)0;
+        } else {
+            const bool zero = l == 0 ? zero_first != 0 : !t.warm;
+            const T* const gu = t.u[l] + (int64_t)m * n;
+            for (int64_t s = tid; s < n; s += nt) lu[s] = zero ? (T)0 : gu[s];
+        }
         if (l == 0) {
             const T* const gf = t.f[0] + (int64_t)m * n;
             for (int64_t s = tid; s < n; s += nt) lu[n + s] = gf[s];
@@ -444,9 +561,9 @@ __global__ __launch_bounds__(1024) void k_batch_tail(const BTail<T, DIM>* __rest
     }
     __syncthreads();
     unsigned in_t = 0;  // bit l: level l's current u is in its Jacobi target buffer
-    const int nops = t.nops[fcycle];
+    const int nops = FMG ? t.nfprog : t.nops[fcycle];
     for (int p = 0; p < nops; ++p) {
-        const uint32_t w = t.ops[fcycle][p];
+        const uint32_t w = FMG ? t.fprog[p] : t.ops[fcycle][p];
         const int op = (int)(w & 15u), l = (int)((w >> 4) & 15u), arg = (int)(w >> 8);
         const BLev<T, DIM>& L = t.lev[l];
         const int64_t n = L.slots;
@@ -478,6 +595,14 @@ __global__ __launch_bounds__(1024) void k_batch_tail(const BTail<T, DIM>* __rest
             const int64_t nc = t.lev[l + 1].slots;
             const T* const V = lds + t.off[l + 1] + (((in_t >> (l + 1)) & 1u) ? 2 * nc : 0);
             prolong_part<T, DIM>(u, V, L, t.lev[l + 1].g, t.lev[l + 1].op.cl, t.linear, tid, nt);
+            __syncthreads();
+        } else if (FMG && op == TAIL_FMG_RESTRICT) {
+            restrict_field_part<T, DIM>(f, lds + t.off[l + 1] + t.lev[l + 1].slots, mgeo(L.g), mgeo(t.lev[l + 1].g), tid, nt);
+            __syncthreads();
+        } else if (FMG && op == TAIL_FMG_PROLONG) {
+            const int64_t nc = t.lev[l + 1].slots;
+            const T* const V = lds + t.off[l + 1] + (((in_t >> (l + 1)) & 1u) ? 2 * nc : 0);
+            fmg_prolong_part<T, DIM>(u, V, mgeo(L.g), mgeo(t.lev[l + 1].g), -t.lev[l + 1].op.cl, tid, nt);
             __syncthreads();
         }
     }
@@ -560,6 +685,14 @@ struct mgp_batch {
     bool use_graph = true;
     hipGraphExec_t exec = nullptr;
     int64_t launches = 0, last_launches = 0;
+    // mgp_batch_fmg: the LDS ascent's program and the captured ascent, each for the last cycles_per_level used
+    uint32_t* d_fprog = nullptr;
+    int fprog_cycles = 0;         // 0: none built
+    bool fprog_piece = false;     // the program is over kFmgMaxOps: the tail levels' ascent runs per piece
+    hipGraphExec_t fmg_exec = nullptr;
+    int fmg_exec_cycles = 0;
+    int64_t fmg_launches = 0;
+    bool old_stale = false;       // psiOld describes an iterate that is gone (until the next outer iteration)
     mutable std::string err;
 
     int fail(int code, const char* fmt, ...) const
@@ -780,7 +913,7 @@ struct Cycle {
         const int last = (int)b->lev.size() - 1;
         BHostLevel& L = b->lev[l];
         if (l == b->T) {
-            BLAUNCH(b, (mgp::k_batch_tail<T, DIM>), b->B, b->tail_threads, b->tail_lds,
+            BLAUNCH(b, (mgp::k_batch_tail<T, DIM, false>), b->B, b->tail_threads, b->tail_lds,
                     (const mgp::BTail<T, DIM>*)b->d_tail, fcycle ? 1 : 0, zero ? 1 : 0, active());
             return MGP_OK;
         }
@@ -811,18 +944,83 @@ struct Cycle {
         }
         return smooth(l, b->o.nu2);
     }
+    // an odd number of Jacobi sweeps leaves a level's result in its target buffer: back into u
+    int fold()
+    {
+        for (auto& L : b->lev)
+            if (L.cur) {
+                BTRY(copy((const T*)L.t, (T*)L.u, L.slots));
+                L.cur = 0;
+            }
+        return MGP_OK;
+    }
+    // f of level l + 1 = R f of level l; act: the members it runs on (nullptr: all)
+    int fmg_restrict(int l, const int* act)
+    {
+        const BHostLevel& L = b->lev[l];
+        const BHostLevel& C = b->lev[l + 1];
+        const int nb = piece_blocks(C.slots);
+        BLAUNCH(b, (mgp::k_batch_restrict_field<T, DIM>), (int64_t)b->B * nb, kBlock, 0, F(l), F(l + 1), L.g, C.g, nb, act);
+        return MGP_OK;
+    }
+    // the current u of level l = P3 (the current u of level l + 1): the marching vector form where a coarse row holds
+    // 16 bytes of reals, the scalar part function below that
+    int fmg_p3(int l, const int* act)
+    {
+        const BHostLevel& L = b->lev[l];
+        const BHostLevel& C = b->lev[l + 1];
+        if ((int64_t)C.g.nx * b->rb >= 16) {
+            BHIP(b, mgp::launch_fmg_prolong_batch(b->rb, DIM, U(l), U(l + 1), L.g, C.g, C.cl, b->B, L.slots, C.slots, act, b->s));
+            ++b->launches;
+        } else {
+            const int nb = piece_blocks(L.slots);
+            BLAUNCH(b, (mgp::k_batch_fmg_prolong<T, DIM>), (int64_t)b->B * nb, kBlock, 0, U(l), U(l + 1), L.g, C.g, -(T)C.cl, nb,
+                    act);
+        }
+        return MGP_OK;
+    }
+    int zero_level(int l)
+    {
+        BHostLevel& L = b->lev[l];
+        L.cur = 0;
+        return copy(nullptr, U(l), L.slots);
+    }
+    // Steps 1-4 of mgp_fmg on every armed member.  The levels from T down are ONE launch (the LDS ascent: the
+    // restrictions from T, the coarse solve, every P3 and per-level cycle up to level T); with no LDS engine, or a
+    // program over kFmgMaxOps, they run per piece like the levels above.
+    int fmg_ascent(int cycles)
+    {
+        const int last = (int)b->lev.size() - 1, T0 = b->T;
+        const bool fcycle = b->o.cycle == MGP_CYCLE_F;
+        const bool lds = T0 >= 0 && !b->fprog_piece;
+        for (int l = 0; l < (lds ? T0 : last); ++l) BTRY(fmg_restrict(l, active()));
+        int from;  // the first level a per-piece P3 writes
+        if (lds) {
+            BLAUNCH(b, (mgp::k_batch_tail<T, DIM, true>), b->B, std::min(b->tail_threads, mgp::tail_max_threads<T, DIM>(true)),
+                    b->tail_lds,
+                    (const mgp::BTail<T, DIM>*)b->d_tail, 0, 0, active());
+            from = T0 - 1;
+        } else {
+            BTRY(zero_level(last));
+            BTRY(smooth(last, b->lev[last].cells == 1 ? 1 : b->o.coarse_sweeps));
+            from = last - 1;
+        }
+        for (int l = from; l >= 0; --l) {
+            BTRY(fmg_p3(l, active()));
+            BTRY(zero_level(l + 1));
+            if (l == 0) break;
+            for (int k = 0; k < cycles; ++k) BTRY(rec(l, fcycle, false));
+            if (!lds && T0 >= 0) BTRY(fold());  // (the LDS engine's cycle reads its levels' u buffers)
+        }
+        return fold();
+    }
     // One outer iteration of every active member (cpu.lua:196-206)
     int outer()
     {
         BHostLevel& L0 = b->lev[0];
         if (b->o.err_mode) BTRY(copy((const T*)L0.u, (T*)b->old, L0.slots));
         BTRY(rec(0, b->o.cycle == MGP_CYCLE_F, false));
-        // an odd number of Jacobi sweeps leaves a level's result in its target buffer: back into u
-        for (auto& L : b->lev)
-            if (L.cur) {
-                BTRY(copy((const T*)L.t, (T*)L.u, L.slots));
-                L.cur = 0;
-            }
+        BTRY(fold());
         if (b->o.err_mode) {
             BLAUNCH(b, (mgp::k_batch_err<T>), (int64_t)b->B * b->nbe, kBlock, 0, (const T*)L0.u, (const T*)b->old, L0.slots, b->nbe,
                     b->d_part, active());
@@ -871,6 +1069,126 @@ int enqueue_cycles(mgp_batch* b, int k)
     return MGP_OK;
 }
 
+// The LDS ascent's program for `cycles` cycles per level, levels relative to T; generation stops once it is over `cap`
+void fmg_gen(const mgp_batch* b, int cycles, size_t cap, std::vector<uint32_t>& ops)
+{
+    const int T = b->T, last = (int)b->lev.size() - 1;
+    const bool fcycle = b->o.cycle == MGP_CYCLE_F;
+    auto emit = [&](int op, int lv) { ops.push_back((uint32_t)op | ((uint32_t)(lv - T) << 4)); };
+    for (int l = T; l < last; ++l) emit(mgp::TAIL_FMG_RESTRICT, l);
+    emit(mgp::TAIL_ZERO, last);
+    tail_gen(b, T, last, false, ops);
+    for (int l = last - 1; l >= T; --l) {
+        emit(mgp::TAIL_FMG_PROLONG, l);
+        emit(mgp::TAIL_ZERO, l + 1);
+        for (int k = 0; k < cycles && l >= 1; ++k) {
+            tail_gen(b, T, l, fcycle, ops);
+            if (ops.size() > cap) return;
+        }
+    }
+}
+
+// A program longer than this runs the tail levels' ascent per piece (cycles_per_level <= 2 stays far below it on every
+// tail plan_tail admits: at most 1100 ops for 8 levels and F-cycles)
+constexpr size_t kFmgMaxOps = 4096;
+
+// What the ascent needs before it is enqueued (never inside a capture): the program on the device, or, when it runs
+// the tail levels per piece, their Jacobi target buffers
+int fmg_prepare(mgp_batch* b, int cycles)
+{
+    if (b->T < 0) return MGP_OK;
+    if (b->fprog_cycles != cycles) {
+        std::vector<uint32_t> ops;
+        fmg_gen(b, cycles, kFmgMaxOps, ops);
+        BHIP(b, hipStreamSynchronize(b->s));
+        b->fprog_cycles = 0;
+        b->fprog_piece = ops.size() > kFmgMaxOps;
+        if (!b->fprog_piece) {
+            if (b->d_fprog) (void)hipFree(b->d_fprog);
+            b->d_fprog = nullptr;
+            if (hipMalloc((void**)&b->d_fprog, ops.size() * sizeof(uint32_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                return b->fail(MGP_ERR_OOM, "hipMalloc failed for the ascent's program (%zu ops)", ops.size());
+            }
+            BHIP(b, hipMemcpy(b->d_fprog, ops.data(), ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            struct {
+                const uint32_t* fprog;
+                int nfprog;
+            } ref{b->d_fprog, (int)ops.size()};  // BTail's last two members, uploaded together
+            BTRY(dispatch(b, [&](auto t, auto d) {
+                using BT = mgp::BTail<decltype(t), decltype(d)::value>;
+                static_assert(offsetof(BT, nfprog) == offsetof(BT, fprog) + sizeof(ref.fprog), "fprog, nfprog are adjacent");
+                BHIP(b, hipMemcpy((char*)b->d_tail + offsetof(BT, fprog), &ref, sizeof(ref.fprog) + sizeof(ref.nfprog),
+                                  hipMemcpyHostToDevice));
+                return (int)MGP_OK;
+            }));
+        }
+        b->fprog_cycles = cycles;
+    }
+    if (b->fprog_piece && b->o.smoother == MGP_JACOBI)
+        for (size_t l = b->T; l < b->lev.size(); ++l) {
+            BHostLevel& L = b->lev[l];
+            if (L.t) continue;
+            const size_t bytes = (size_t)b->B * L.slots * b->rb;
+            if (hipMalloc((void**)&L.t, bytes) != hipSuccess) {
+                L.t = nullptr;
+                (void)hipGetLastError();
+                return b->fail(MGP_ERR_OOM, "hipMalloc failed for the Jacobi buffer of level %d", (int)l);
+            }
+            BHIP(b, hipMemset(L.t, 0, bytes));
+        }
+    return MGP_OK;
+}
+
+// (a pass that fails part-way leaves the Jacobi levels' host-side buffer toggles where it stopped: back to u)
+int enqueue_ascent_once(mgp_batch* b, int cycles)
+{
+    const int rc = dispatch(b, [&](auto t, auto d) {
+        Cycle<decltype(t), decltype(d)::value> c{b};
+        return c.fmg_ascent(cycles);
+    });
+    if (rc != MGP_OK)
+        for (auto& L : b->lev) L.cur = 0;
+    return rc;
+}
+
+// The ascent on the stream: a replay of its captured graph (one linear chain, kept for the last cycles_per_level), or
+// eager launches
+int enqueue_ascent(mgp_batch* b, int cycles)
+{
+    BTRY(fmg_prepare(b, cycles));
+    if (b->use_graph && (!b->fmg_exec || b->fmg_exec_cycles != cycles)) {
+        if (b->fmg_exec) {
+            BHIP(b, hipStreamSynchronize(b->s));
+            (void)hipGraphExecDestroy(b->fmg_exec);
+            b->fmg_exec = nullptr;
+        }
+        BHIP(b, hipStreamBeginCapture(b->s, hipStreamCaptureModeThreadLocal));
+        b->launches = 0;
+        const int rc = enqueue_ascent_once(b, cycles);
+        hipGraph_t graph = nullptr;
+        const hipError_t ec = hipStreamEndCapture(b->s, &graph);
+        if (rc != MGP_OK) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return rc;
+        }
+        BHIP(b, ec);
+        const hipError_t ei = hipGraphInstantiate(&b->fmg_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        BHIP(b, ei);
+        b->fmg_exec_cycles = cycles;
+        b->fmg_launches = b->launches;
+    }
+    if (b->fmg_exec) {
+        BHIP(b, hipGraphLaunch(b->fmg_exec, b->s));
+    } else {
+        b->launches = 0;
+        BTRY(enqueue_ascent_once(b, cycles));
+        b->fmg_launches = b->launches;
+    }
+    return MGP_OK;
+}
+
 int arm(mgp_batch* b, int stop, double eps)
 {
     mgp::k_batch_arm<<<dim3((unsigned)((b->B + kBlock - 1) / kBlock)), dim3(kBlock), 0, b->s>>>(b->B, stop, eps, b->st);
@@ -882,13 +1200,14 @@ void batch_free(mgp_batch* b)
 {
     if (!b) return;
     if (b->exec) (void)hipGraphExecDestroy(b->exec);
+    if (b->fmg_exec) (void)hipGraphExecDestroy(b->fmg_exec);
     for (auto& L : b->lev) {
         if (L.u) (void)hipFree(L.u);
         if (L.f) (void)hipFree(L.f);
         if (L.t) (void)hipFree(L.t);
     }
     for (void* p : {(void*)b->old, (void*)b->d_tail, (void*)b->st.active, (void*)b->st.iters, (void*)b->st.last_err,
-                    (void*)b->st.ctr, (void*)b->st.eps, (void*)b->st.errs, (void*)b->d_part, (void*)b->d_norm})
+                    (void*)b->st.ctr, (void*)b->st.eps, (void*)b->st.errs, (void*)b->d_part, (void*)b->d_norm, (void*)b->d_fprog})
         if (p) (void)hipFree(p);
     if (b->h_nactive) (void)hipHostFree(b->h_nactive);
     if (b->s) (void)hipStreamDestroy(b->s);
@@ -920,7 +1239,10 @@ int upload_tail(mgp_batch* b)
     hipError_t e = hipMalloc(&b->d_tail, sizeof(*t));
     if (e == hipSuccess) e = hipMemcpy(b->d_tail, t, sizeof(*t), hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)mgp::k_batch_tail<T, DIM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute((const void*)mgp::k_batch_tail<T, DIM, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)mgp::kTailMaxLds);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)mgp::k_batch_tail<T, DIM, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)mgp::kTailMaxLds);
     delete t;
     if (e == hipErrorOutOfMemory) return b->fail(MGP_ERR_OOM, "hipMalloc failed for the coarse program");
@@ -944,6 +1266,9 @@ int field_ptr(const mgp_batch* b, int member, int level, int which, int64_t coun
         *base = L.f;
     else if (which == MGP_FIELD_PSI_OLD && level == 0 && !set) {
         if (!b->o.err_mode) return b->fail(MGP_ERR_STATE, "MGP_FIELD_PSI_OLD needs err_mode 1");
+        if (b->old_stale)
+            return b->fail(MGP_ERR_STATE, "MGP_FIELD_PSI_OLD: psi was replaced by the full multigrid start; psiOld is "
+                                          "valid again after the next outer iteration");
         *base = b->old;
     } else
         return b->fail(MGP_ERR_ARG, "field %d is not %s on a batch", which, set ? "writable" : "readable");
@@ -992,6 +1317,26 @@ int field_io(mgp_batch* b, int member, int level, int which, void* buf, int64_t 
     if (e == hipSuccess) e = hipStreamSynchronize(b->s);
     if (stage) (void)hipFree(stage);
     BHIP(b, e);
+    return MGP_OK;
+}
+
+// k outer iterations of the armed members and the one synchronisation at the end (one more per full errs buffer)
+int cycles_armed(mgp_batch* b, int32_t k, double* errs)
+{
+    if (k > 0) b->old_stale = false;
+    for (int64_t done = 0; done < k;) {
+        const int n = (int)std::min<int64_t>(b->chunk, k - done);
+        BHIP(b, hipMemsetAsync(b->st.ctr, 0, sizeof(int), b->s));
+        BTRY(enqueue_cycles(b, n));
+        if (errs && b->o.err_mode)
+            BHIP(b, hipMemcpyAsync(errs + done * b->B, b->st.errs, sizeof(double) * (size_t)n * b->B, hipMemcpyDeviceToHost,
+                                   b->s));
+        if (done + n < k) BHIP(b, hipStreamSynchronize(b->s));  // (the errs buffer is reused by the next chunk)
+        done += n;
+    }
+    BHIP(b, hipStreamSynchronize(b->s));
+    if (errs && !b->o.err_mode)
+        for (int64_t i = 0; i < (int64_t)k * b->B; ++i) errs[i] = NAN;
     return MGP_OK;
 }
 
@@ -1164,20 +1509,7 @@ int mgp_batch_cycles(mgp_batch* b, int32_t k, double* errs)
     if (!b) return MGP_ERR_ARG;
     if (k < 0) return b->fail(MGP_ERR_ARG, "k must be >= 0");
     BTRY(arm(b, 0, 0.0));
-    for (int64_t done = 0; done < k;) {
-        const int n = (int)std::min<int64_t>(b->chunk, k - done);
-        BHIP(b, hipMemsetAsync(b->st.ctr, 0, sizeof(int), b->s));
-        BTRY(enqueue_cycles(b, n));
-        if (errs && b->o.err_mode)
-            BHIP(b, hipMemcpyAsync(errs + done * b->B, b->st.errs, sizeof(double) * (size_t)n * b->B, hipMemcpyDeviceToHost,
-                                   b->s));
-        if (done + n < k) BHIP(b, hipStreamSynchronize(b->s));  // (the errs buffer is reused by the next chunk)
-        done += n;
-    }
-    BHIP(b, hipStreamSynchronize(b->s));
-    if (errs && !b->o.err_mode)
-        for (int64_t i = 0; i < (int64_t)k * b->B; ++i) errs[i] = NAN;
-    return MGP_OK;
+    return cycles_armed(b, k, errs);
 }
 
 int mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iters, double* last_err)
@@ -1187,6 +1519,7 @@ int mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iter
     if (maxiter < 0) return b->fail(MGP_ERR_ARG, "maxiter must be >= 0");
     constexpr int kSolveChunk = 4;  // cycles enqueued between two looks at the number of active members
     BTRY(arm(b, 1, epsilon));
+    if (maxiter > 0) b->old_stale = false;
     for (int done = 0; done < maxiter;) {
         const int n = (int)std::min<int64_t>(std::min<int64_t>(kSolveChunk, b->chunk), maxiter - done);
         BHIP(b, hipMemsetAsync(b->st.ctr, 0, sizeof(int), b->s));
@@ -1255,6 +1588,49 @@ int mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means)
     BHIP(b, hipMemcpyAsync(h.data(), b->d_norm + b->B, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b->s));
     BHIP(b, hipStreamSynchronize(b->s));
     if (means) std::copy(h.begin(), h.end(), means);
+    return MGP_OK;
+}
+
+int mgp_batch_fmg_restrict_rhs(mgp_batch* b, int level)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (level < 0 || level + 1 >= (int)b->lev.size()) return b->fail(MGP_ERR_ARG, "mgp_batch_fmg_restrict_rhs: bad level %d", level);
+    BTRY(dispatch(b, [&](auto t, auto d) {
+        Cycle<decltype(t), decltype(d)::value> c{b};
+        return c.fmg_restrict(level, nullptr);
+    }));
+    BHIP(b, hipStreamSynchronize(b->s));
+    return MGP_OK;
+}
+
+int mgp_batch_fmg_prolong(mgp_batch* b, int level)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (level < 0 || level + 1 >= (int)b->lev.size()) return b->fail(MGP_ERR_ARG, "mgp_batch_fmg_prolong: bad level %d", level);
+    BTRY(dispatch(b, [&](auto t, auto d) {
+        Cycle<decltype(t), decltype(d)::value> c{b};
+        return c.fmg_p3(level, nullptr);
+    }));
+    if (level == 0) b->old_stale = true;  // psiOld describes an iterate that is gone
+    BHIP(b, hipStreamSynchronize(b->s));
+    return MGP_OK;
+}
+
+int mgp_batch_fmg(mgp_batch* b, int32_t cycles_per_level, int32_t final_cycles, double* errs)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (cycles_per_level < 1 || final_cycles < 0)
+        return b->fail(MGP_ERR_ARG, "mgp_batch_fmg: cycles_per_level >= 1 and final_cycles >= 0");
+    BTRY(arm(b, 0, 0.0));
+    b->old_stale = true;  // (before the first launch: an ascent that fails part-way has replaced psi already)
+    BTRY(enqueue_ascent(b, cycles_per_level));
+    return cycles_armed(b, final_cycles, errs);
+}
+
+int mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent)
+{
+    if (!b || !ascent) return MGP_ERR_ARG;
+    *ascent = b->fmg_launches;
     return MGP_OK;
 }
 

@@ -28,52 +28,16 @@
 // 1/8 of the fine one); no LDS.  Scalar form: a thread per fine slot (any sizes: coarse nx below the vector width,
 // one- and two-cell coarse axes).  Both evaluate exactly the expressions above.
 //
+// A batch (mgp_batch.hip) runs the vector form on all its members in one launch: k_fmg_prolong_b / k_fmg_prolong_2d_b are
+// the same march (fmg_march / fmg_march_2d) with a member stride for u and V and a number of workgroups per member;
+// the small helpers of P3 (W3, cub, ext_src, ext_scale) are in mgp_fmg_dev.h for both translation units.
+//
 // One rank's whole box only (g.z0 = 0, every plane local): the cubic stencil needs a second coarse ghost plane that a
 // slab level does not carry.
-#include "mgp_device.h"
+#include "mgp_fmg_dev.h"
 
 namespace mgp {
 namespace {
-
-template <typename T>
-struct W3 {
-    static constexpr T wp = (T)(105.0 / 128.0), wn = (T)(35.0 / 128.0), wq = (T)(-7.0 / 128.0), wr = (T)(-5.0 / 128.0);
-};
-
-// ((wp a + wn b) + wq c) + wr d
-template <typename T>
-__device__ __forceinline__ T cub(T a, T b, T c, T d)
-{
-    T s = W3<T>::wp * a + W3<T>::wn * b;
-    s = s + W3<T>::wq * c;
-    s = s + W3<T>::wr * d;
-    return s;
-}
-
-// sample q in [-2, m + 1] of the extended line: the in-box sample it comes from, and how many times mc multiplies it
-__device__ __forceinline__ int ext_src(int q, int m, int& nmul)
-{
-    nmul = 0;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        if (q < 0) {
-            q = -1 - q;
-            ++nmul;
-        } else if (q >= m) {
-            q = 2 * m - 1 - q;
-            ++nmul;
-        }
-    }
-    return q;
-}
-
-template <typename T>
-__device__ __forceinline__ T ext_scale(T v, int nmul, T mc)
-{
-    if (nmul >= 1) v = mc * v;
-    if (nmul >= 2) v = mc * v;
-    return v;
-}
 
 // ---- scalar form: a thread per fine slot ------------------------------------------------------------------
 
@@ -218,14 +182,14 @@ __device__ __forceinline__ void z_sample(const T* __restrict__ V, const Geo& gc,
 // 3D: the thread marches through `zc` coarse planes of its column (J, I0 ..) with the x, y-interpolated planes
 // K - 2 .. K + 2 in registers: every step computes one new plane (a ghost plane from the in-box plane it mirrors) and
 // stores the 2 x 2 fine rows above coarse row (J, K).  zc = 1 is a thread per coarse row.
+// (lb: the workgroup's index within its box; < 0: the grid is one box, XCD-remapped)
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_fmg_prolong(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc, T mc,
-                                                        int zc)
+__device__ __forceinline__ void fmg_march(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc, T mc, int zc, int lb)
 {
     constexpr int N = VN<T>::n;
     constexpr int LN = N == 4 ? 2 : 1;
     const int lgpr = gc.lx - LN;  // log2 groups of N per coarse row
-    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = lb < 0 ? xcd_remap(blockIdx.x, gridDim.x) : lb;
     const int64_t it = (int64_t)b * kBlock + threadIdx.x;
     const int grp = (int)(it & ((1 << lgpr) - 1));
     const int J = (int)((it >> lgpr) & (gc.ny - 1));
@@ -263,15 +227,34 @@ __global__ __launch_bounds__(kBlock) void k_fmg_prolong(T* __restrict__ u, const
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_fmg_prolong(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc, T mc,
+                                                        int zc)
+{
+    fmg_march<T>(u, V, g, gc, mc, zc, -1);
+}
+
+// The same march on every member of a batch (mgp_batch.hip): workgroups [m * nb, (m + 1) * nb) work on member m, whose
+// u / V start us / vs reals after member m - 1's; active == nullptr: every member
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_fmg_prolong_b(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc,
+                                                          T mc, int zc, int64_t us, int64_t vs, int nb,
+                                                          const int* __restrict__ active)
+{
+    const int m = (int)(blockIdx.x / (unsigned)nb);
+    if (active && !active[m]) return;
+    fmg_march<T>(u + m * us, V + m * vs, g, gc, mc, zc, (int)(blockIdx.x - (unsigned)m * nb));
+}
+
 // 2D: the same march through `yc` coarse rows with the x-interpolated rows J - 2 .. J + 2 in registers
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_fmg_prolong_2d(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc,
-                                                           T mc, int yc)
+__device__ __forceinline__ void fmg_march_2d(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc, T mc, int yc,
+                                             int lb)
 {
     constexpr int N = VN<T>::n;
     constexpr int LN = N == 4 ? 2 : 1;
     const int lgpr = gc.lx - LN;
-    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = lb < 0 ? xcd_remap(blockIdx.x, gridDim.x) : lb;
     const int64_t it = (int64_t)b * kBlock + threadIdx.x;
     const int grp = (int)(it & ((1 << lgpr) - 1));
     const int64_t chunk = it >> lgpr;
@@ -311,6 +294,23 @@ __global__ __launch_bounds__(kBlock) void k_fmg_prolong_2d(T* __restrict__ u, co
         store_row<T, N>(u, g, 2 * J, 0, I0, ye);
         store_row<T, N>(u, g, 2 * J + 1, 0, I0, yo);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_fmg_prolong_2d(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc,
+                                                           T mc, int yc)
+{
+    fmg_march_2d<T>(u, V, g, gc, mc, yc, -1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_fmg_prolong_2d_b(T* __restrict__ u, const T* __restrict__ V, Geo g, Geo gc,
+                                                             T mc, int yc, int64_t us, int64_t vs, int nb,
+                                                             const int* __restrict__ active)
+{
+    const int m = (int)(blockIdx.x / (unsigned)nb);
+    if (active && !active[m]) return;
+    fmg_march_2d<T>(u + m * us, V + m * vs, g, gc, mc, yc, (int)(blockIdx.x - (unsigned)m * nb));
 }
 
 // ---- the 2^d average of a field ------------------------------------------------------------------------------
@@ -421,6 +421,28 @@ hipError_t fmg_prolong_t(void* u, const void* V, Geo g, Geo gc, double clc, hipS
     return hipGetLastError();
 }
 
+// The vector form on B members: the march length from B x the member's columns, so that the batch fills the machine
+// as one box of its size would
+template <typename T, int D>
+hipError_t fmg_prolong_batch_t(void* u, const void* V, Geo g, Geo gc, double clc, int B, int64_t us, int64_t vs,
+                               const int* active, hipStream_t s)
+{
+    constexpr int n = VN<T>::n;
+    const T mc = -(T)clc;
+    const int64_t groups = gc.nx / n;
+    if (D == 3) {
+        const int zc = march_len((int64_t)B * groups * gc.ny, (int)gc.nz);
+        const int nb = (int)nblk(groups * gc.ny * (gc.nz / zc));
+        k_fmg_prolong_b<T><<<(unsigned)((int64_t)B * nb), kBlock, 0, s>>>((T*)u, (const T*)V, g, gc, mc, zc, us, vs, nb, active);
+    } else {
+        const int yc = march_len((int64_t)B * groups, gc.ny);
+        const int nb = (int)nblk(groups * (gc.ny / yc));
+        k_fmg_prolong_2d_b<T><<<(unsigned)((int64_t)B * nb), kBlock, 0, s>>>((T*)u, (const T*)V, g, gc, mc, yc, us, vs, nb,
+                                                                            active);
+    }
+    return hipGetLastError();
+}
+
 template <typename T, int D>
 hipError_t restrict_field_t(const void* f, void* R, Geo g, Geo gc, hipStream_t s)
 {
@@ -443,6 +465,20 @@ hipError_t launch_fmg_prolong(int rb, int dim, void* u, const void* V, Geo g, Ge
         return hipErrorInvalidValue;
     if (rb == 8) return dim == 3 ? fmg_prolong_t<double, 3>(u, V, g, gc, clc, s) : fmg_prolong_t<double, 2>(u, V, g, gc, clc, s);
     return dim == 3 ? fmg_prolong_t<float, 3>(u, V, g, gc, clc, s) : fmg_prolong_t<float, 2>(u, V, g, gc, clc, s);
+}
+
+hipError_t launch_fmg_prolong_batch(int rb, int dim, void* u, const void* V, Geo g, Geo gc, double clc, int B, int64_t us,
+                                    int64_t vs, const int* active, hipStream_t s)
+{
+    if ((rb != 4 && rb != 8) || B < 1 || gc.nx * rb < 16 || g.z0 != 0 || gc.z0 != 0 || g.nz != g.gnz || gc.nz != gc.gnz ||
+        g.P != 2 * g.H || gc.P != 2 * gc.H || g.nx != 2 * gc.nx || g.ny != 2 * gc.ny || g.nz != (dim == 3 ? 2 : 1) * gc.nz ||
+        us < g.P * g.nz || vs < gc.P * gc.nz || (us * rb) % 16 != 0)
+        return hipErrorInvalidValue;
+    if (rb == 8)
+        return dim == 3 ? fmg_prolong_batch_t<double, 3>(u, V, g, gc, clc, B, us, vs, active, s)
+                        : fmg_prolong_batch_t<double, 2>(u, V, g, gc, clc, B, us, vs, active, s);
+    return dim == 3 ? fmg_prolong_batch_t<float, 3>(u, V, g, gc, clc, B, us, vs, active, s)
+                    : fmg_prolong_batch_t<float, 2>(u, V, g, gc, clc, B, us, vs, active, s);
 }
 
 hipError_t launch_restrict_field(int rb, int dim, const void* f, void* R, Geo g, Geo gc, hipStream_t s)

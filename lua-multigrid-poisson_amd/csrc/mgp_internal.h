@@ -154,6 +154,13 @@ hipError_t launch_prolong_correct(int rb, int dim, int linear, void* u, const vo
 // the expressions).  V's and u's ghost planes are not read.
 hipError_t launch_restrict_field(int rb, int dim, const void* f, void* R, Geo g, Geo gc, hipStream_t s);
 hipError_t launch_fmg_prolong(int rb, int dim, void* u, const void* V, Geo g, Geo gc, double clc, hipStream_t s);
+// launch_fmg_prolong's vector form on the B members of a batch (mgp_batch.hip) in one launch: member m's u / V start
+// m * us / m * vs reals into the buffers; active (device, may be nullptr: every member) skips the members whose entry
+// is 0.  The vector form needs coarse rows of at least 16 bytes of reals: the batch tests that itself and runs its
+// scalar form on smaller levels, so hipErrorInvalidValue (that condition, or inconsistent geometries or strides) is
+// an error to it like any other.
+hipError_t launch_fmg_prolong_batch(int rb, int dim, void* u, const void* V, Geo g, Geo gc, double clc, int B, int64_t us,
+                                    int64_t vs, const int* active, hipStream_t s);
 // Deterministic two-pass fp64 sum of (a - b)^2 over n elements into *out (ctr != nullptr: into
 // out[*ctr], then ++*ctr on the device).
 // lev (here and in launch_metrics): a and b are whole levels of that layout, n = lev->P * planes.  The sum then runs
@@ -322,7 +329,8 @@ hipError_t blk2_attr(int rb);
 constexpr int kTailMaxLevels = 8;
 constexpr int kTailMaxOps = 192;
 constexpr size_t kTailMaxLds = 160 * 1024;  // gfx950 LDS per workgroup
-enum TailOp { TAIL_SMOOTH = 1, TAIL_RR = 2, TAIL_ZERO = 3, TAIL_PROLONG = 4 };
+// (TAIL_FMG_*: the batch's LDS ascent only, mgp_batch.hip: f of level + 1 = R f of level; u of level = P3 u of level + 1)
+enum TailOp { TAIL_SMOOTH = 1, TAIL_RR = 2, TAIL_ZERO = 3, TAIL_PROLONG = 4, TAIL_FMG_RESTRICT = 5, TAIL_FMG_PROLONG = 6 };
 struct TailSpec {
     int nlev, nops, jacobi, linear;
     int zero_first;  // the first level's u is logically 0 (a fresh guess): loaded as zeros

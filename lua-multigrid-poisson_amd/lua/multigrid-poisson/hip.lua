@@ -138,6 +138,10 @@ int         mgp_batch_cycles(mgp_batch* b, int32_t k, double* errs);
 int         mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iters, double* last_err);
 int         mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm);
 int         mgp_batch_launches(const mgp_batch* b, int64_t* per_cycle);
+int         mgp_batch_fmg_restrict_rhs(mgp_batch* b, int level);
+int         mgp_batch_fmg_prolong(mgp_batch* b, int level);
+int         mgp_batch_fmg(mgp_batch* b, int32_t cycles_per_level, int32_t final_cycles, double* errs);
+int         mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent);
 ]]
 
 local lib = ffi.load(os.getenv('MGP_LIBRARY') or 'mgpoisson')
@@ -653,6 +657,31 @@ end
 function MGBatch:launches()
 	local n = ffi.new('int64_t[1]')
 	checkBatch(lib.mgp_batch_launches(self.handle, n), self.handle)
+	return tonumber(n[0])
+end
+
+-- full multigrid start of every member (mgp_batch_fmg; MultigridHIP:fmg per member): psi from f alone, then `final`
+-- outer iterations; returns the errs of the last one (double[batch]; nil with final = 0).  boundary = 'neumann': every
+-- member's f loses its mean first and its psi afterwards
+function MGBatch:fmg(cycles, final)
+	cycles, final = cycles or 1, final or 1
+	if self.boundary == 'neumann' then self:removeMean('f') end
+	local errs = ffi.new('double[?]', math.max(final, 1) * self.batch)
+	checkBatch(lib.mgp_batch_fmg(self.handle, cycles, final, errs), self.handle)
+	if self.boundary == 'neumann' then self:removeMean('psi') end
+	if final < 1 then return nil end
+	local last = ffi.new('double[?]', self.batch)
+	for m = 0, self.batch - 1 do last[m] = errs[(final - 1) * self.batch + m] end
+	return last
+end
+
+function MGBatch:fmgRestrictRhs(level) checkBatch(lib.mgp_batch_fmg_restrict_rhs(self.handle, level), self.handle) end
+function MGBatch:fmgProlong(level) checkBatch(lib.mgp_batch_fmg_prolong(self.handle, level), self.handle) end
+
+-- kernel launches of the last fmg() call's ascent (independent of batch)
+function MGBatch:fmgLaunches()
+	local n = ffi.new('int64_t[1]')
+	checkBatch(lib.mgp_batch_fmg_launches(self.handle, n), self.handle)
 	return tonumber(n[0])
 end
 

@@ -169,6 +169,10 @@ SIGNATURES = {
     "mgp_batch_solve": (ctypes.c_int, [_vp, _dbl, _i32, _P(_i32), _P(_dbl)]),
     "mgp_batch_residual_norm": (ctypes.c_int, [_vp, _P(_dbl), _P(_dbl)]),
     "mgp_batch_launches": (ctypes.c_int, [_vp, _P(_i64)]),
+    "mgp_batch_fmg_restrict_rhs": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "mgp_batch_fmg_prolong": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "mgp_batch_fmg": (ctypes.c_int, [_vp, _i32, _i32, _P(_dbl)]),
+    "mgp_batch_fmg_launches": (ctypes.c_int, [_vp, _P(_i64)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

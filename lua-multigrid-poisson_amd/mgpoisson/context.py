@@ -601,3 +601,24 @@ class BatchContext:
         n = ctypes.c_int64()
         self._chk(L.lib.mgp_batch_launches(self._h, ctypes.byref(n)))
         return n.value
+
+    def fmg(self, cycles: int = 1, final: int = 1) -> np.ndarray:
+        """mgp_batch_fmg: every member's psi from its level-0 f alone (mgp_fmg per member, the ascent one captured graph
+        whose LDS levels are one launch), then ``final`` outer iterations; the (final, B) errs."""
+        errs = np.zeros((max(int(final), 0), self.batch), dtype=np.float64)
+        self._chk(L.lib.mgp_batch_fmg(self._h, int(cycles), int(final), errs.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return errs
+
+    def fmg_restrict_rhs(self, level):
+        """Every member's f of ``level`` + 1 = the restriction of its f of ``level`` (mgp_batch_fmg_restrict_rhs)."""
+        self._chk(L.lib.mgp_batch_fmg_restrict_rhs(self._h, int(level)))
+
+    def fmg_prolong(self, level):
+        """Every member's u of ``level`` = the cubic prolongation of its u of ``level`` + 1 (mgp_batch_fmg_prolong)."""
+        self._chk(L.lib.mgp_batch_fmg_prolong(self._h, int(level)))
+
+    def fmg_launches(self) -> int:
+        """Kernel launches of the last fmg() call's ascent, without the final iterations (independent of B)."""
+        n = ctypes.c_int64()
+        self._chk(L.lib.mgp_batch_fmg_launches(self._h, ctypes.byref(n)))
+        return n.value

@@ -377,6 +377,17 @@ class MultigridHIPBatch:
         if self.boundary == "neumann":
             self.ctx.remove_mean(0, L.FIELD_U)
 
+    def fmg(self, cycles=1, final=1) -> np.ndarray:
+        """Full multigrid start of every member (mgp_batch_fmg; ``MultigridHIP.fmg`` per member): the B errs of the last
+        of the ``final`` outer iterations (NaN with ``final`` = 0).  boundary='neumann': every member's f loses its mean
+        first and its psi afterwards."""
+        if self.boundary == "neumann":
+            self.ctx.remove_mean(0, L.FIELD_F)
+        errs = self.ctx.fmg(cycles, final)
+        if self.boundary == "neumann":
+            self.ctx.remove_mean(0, L.FIELD_U)
+        return errs[-1].copy() if len(errs) else np.full(self.batch, np.nan)
+
 
 def _smoother_name(v):
     if callable(v) and getattr(v, "__name__", "") in ("Jacobi", "GaussSeidel", "RedBlackGaussSeidel"):
