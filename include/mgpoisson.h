@@ -275,6 +275,56 @@ int         mgp_fmg_restrict_rhs(mgp_ctx* c, int level);   /* f of level+1 = R f
 int         mgp_fmg_prolong(mgp_ctx* c, int level);        /* u of level = P3 u of level+1 (replaces u) */
 int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs);
 
+/* MAC-grid pressure projection (build-defined, no reference counterpart): the divergence D of a staggered vector field
+ * into level 0's f, the gradient G of level 0's psi onto the faces, and the one-call composition v <- v - G A^-1 D v
+ * (incompressible flow's pressure projection, MHD's divergence cleaning).  Both operators are single fused passes on
+ * the packed layout.
+ *
+ * Level 0 has nx x ny x nz cells (2D: nz = 1).  T is the context's real type and ih = (T)n[0] (= 1/h, a power of two);
+ * every operation is rounded in T, with no contraction.
+ * Face arrays are lexicographic, x fastest and contiguous, owned by the caller, in host or device memory (mem; e.g. a
+ * PyTorch tensor's data_ptr()), and must not overlap:
+ *     vx[k][j][i], i in [0, nx]: the x face between cells i-1 and i; (nx+1) ny nz reals
+ *     vy[k][j][i], j in [0, ny]: nx (ny+1) nz reals
+ *     vz[k][j][i], k in [0, nz]: nx ny (nz+1) reals; 3D only, ignored (may be NULL) in 2D
+ * Divergence D writes level 0's f:
+ *     f[i,j,k] = (((vx[i+1] - vx[i]) + (vy[j+1] - vy[j])) + (vz[k+1] - vz[k])) ih     (2D: without the z term)
+ * Gradient G, per axis, on the line of psi extended by one ghost per side: mc = -(T)c_0, c_0 level 0's boundary
+ * coefficient (0 zero / consistent, +1 face, -1 Neumann; mgp_level_info);
+ *     E[-1] = mc psi[0],  E[n] = mc psi[n-1]     (one multiplication each, always performed)
+ *     g(face i) = (E[i] - E[i-1]) ih,  i in [0, n]
+ * and a one-cell axis takes both ghosts from its one cell.  op = MGP_GRAD_STORE: the arrays receive g;
+ * MGP_GRAD_SUBTRACT: every face becomes v - g.  So under Neumann a wall face has g = +0 and keeps its bits (a -0 stays
+ * -0), under face Dirichlet the wall gradient is 2 psi / h, and in exact arithmetic D(v - G psi) = f - A psi with A the
+ * level-0 operator (diagonal (-2 dim - nb c_0) / h^2): the projected field is divergence-free to the solver's residual.
+ *
+ * mgp_divergence: its state effects are those of mgp_set_field(c, 0, MGP_FIELD_F, ...): psi, psiOld and the metrics
+ * are untouched; pad slots and ghost planes of f are not written.
+ * mgp_gradient reads the psi that mgp_get_field(c, 0, MGP_FIELD_U, ...) returns and changes nothing in the context.
+ * mgp_project, with one host synchronisation at the end:
+ *   1. f = D v;
+ *   2. under MGP_BC_NEUMANN, f's mean is removed (mgp_remove_mean's arithmetic and state effects);
+ *   3. fmg_cycles >= 1: mgp_fmg(fmg_cycles, cycles); otherwise cycles >= 0 ordinary outer iterations from the stored
+ *      psi (the warm start from the last time step; cycles = 0 leaves psi as stored);
+ *   4. v -= G psi.
+ * norms (may be NULL: the pass is skipped) receives {||f||_2, ||f - A psi||_2}, computed like mgp_residual_norm: the
+ * field's divergence norm before the projection and, by the identity, after it.  psi's mean is not removed: G does not
+ * see it.
+ * Host memory: the arrays go through device buffers allocated for the call (MGP_ERR_OOM if that fails, nothing stays
+ * allocated); device memory is the hot path.  Under mgp_set_debug(c, 1) f after mgp_divergence and the faces after
+ * mgp_gradient are scanned: "found a nan: mgp_divergence" / "found a nan: mgp_gradient, axis a" (MGP_ERR_STATE).
+ *
+ * Refused: NULL context, NULL vx or vy (vz in 3D), unknown mem or op, fmg_cycles < 0 or cycles < 0, an
+ * MGP_ARITH_DOUBLE context: MGP_ERR_ARG; world > 1, loopback and group ranks, MGP_TRANSPORT=rccl ("single-GPU contexts
+ * only") and active refinement: MGP_ERR_STATE; mgp_project with fmg_cycles >= 1: also whatever mgp_fmg refuses.
+ * Limits: no batches (mgp_batch_*), no slab or group contexts, no mixed-precision refinement (real = 'mixed'), constant
+ * density only, no cell-centred vector fields, and the wall value of the pressure is zero (face Dirichlet). */
+enum { MGP_GRAD_STORE = 0, MGP_GRAD_SUBTRACT = 1 };
+int         mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem);
+int         mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem);
+int         mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles,
+                        double norms[2]);
+
 /* The reference's Krylov cross-check (test/converge-multigrid-vs-krylov.lua:38-69, solver.conjgrad) on
  * the device, as an independent second oracle for the converged multigrid answer: matrix-free
  * conjugate gradients on the finest level's operator (same 5-/7-point stencil and box boundary) from

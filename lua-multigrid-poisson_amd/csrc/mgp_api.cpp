@@ -2714,6 +2714,8 @@ static int debug_verdict(mgp_ctx* c)
     HIP_TRY(c, hipMemcpy(&first, c->d_dbg, sizeof(int), hipMemcpyDeviceToHost));
     if (first >= 0 && first < (int)c->dbg_names.size()) {
         c->fail_after_sync = true;
+        if (c->dbg_names[(size_t)first].rfind("mgp_", 0) == 0)  // a call's own output (mgp_divergence, mgp_gradient)
+            return c->fail(MGP_ERR_STATE, "found a nan: %s", c->dbg_names[(size_t)first].c_str());
         return c->fail(MGP_ERR_STATE, "found a nan (cpu-raw.lua:135-139, gpu.lua:279-283): %s",
                        c->dbg_names[(size_t)first].c_str());
     }
@@ -2952,16 +2954,21 @@ int mgp_fmg_prolong(mgp_ctx* c, int level)
     return debug_verdict(c);
 }
 
-int mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs)
+// mgp_fmg's refusals (after the NULL check), and its passes enqueued on the stream without a synchronisation
+// (mgp_fmg, mgp_project)
+static int fmg_check(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles)
 {
-    if (!c) return MGP_ERR_ARG;
     if (cycles_per_level < 1 || final_cycles < 0)
         return c->fail(MGP_ERR_ARG, "mgp_fmg: cycles_per_level >= 1 and final_cycles >= 0");
     TRY(fmg_refuses(c, "mgp_fmg"));
     if (c->handoff_fn) return c->fail(MGP_ERR_STATE, "mgp_fmg: a coarse hand-off is set (mgp_set_coarse_handoff)");
+    return MGP_OK;
+}
+
+static int fmg_enqueue(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles)
+{
     const int last = (int)c->lev.size() - 1;
     const bool fcycle = c->o.cycle == MGP_CYCLE_F;
-    TRY(debug_reset(c));
     c->dbg_cycle = 0;
     for (int l = 0; l < last; ++l) TRY(fmg_restrict_rhs(c, l));
     TRY(zero_level(c, c->lev[last]));
@@ -2978,7 +2985,15 @@ int mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* 
         if (l == 0) break;
         for (int k = 0; k < cycles_per_level; ++k) TRY(cycle_rec(c, l, level_h(c, l), fcycle));
     }
-    TRY(enqueue_cycles(c, final_cycles));
+    return enqueue_cycles(c, final_cycles);
+}
+
+int mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(fmg_check(c, cycles_per_level, final_cycles));
+    TRY(debug_reset(c));
+    TRY(fmg_enqueue(c, cycles_per_level, final_cycles));
     TRY(sync_and_check(c));
     TRY(debug_verdict(c));
     return read_errs(c, final_cycles, errs);
@@ -3067,10 +3082,9 @@ int mgp_metrics(mgp_ctx* c, double* rel_err, int64_t* count, double* frob)
     return MGP_OK;
 }
 
-int mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm)
+// mgp_residual_norm's pass (and all-reduce) enqueued: *res = the device pair {sum (f - A u)^2, sum f^2}
+static int resnorm_enqueue(mgp_ctx* c, int level, double** res)
 {
-    if (!c) return MGP_ERR_ARG;
-    if (check_level(c, level) != MGP_OK) return c->fail(MGP_ERR_ARG, "mgp_residual_norm: bad level %d", level);
     Level& L = c->lev[level];
     TRY(materialize_zero(c, L));
     TRY(exchange(c, L));
@@ -3093,6 +3107,17 @@ int mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm)
         else
             NCCL_CALL(c, c->comm, ncclAllReduce(out, out, 2, ncclDouble, ncclSum, c->comm, c->s), "norm all-reduce");
     }
+    *res = out;
+    return MGP_OK;
+}
+
+int mgp_residual_norm(mgp_ctx* c, int level, double* rnorm, double* fnorm)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (check_level(c, level) != MGP_OK) return c->fail(MGP_ERR_ARG, "mgp_residual_norm: bad level %d", level);
+    WaitScope w(c);  // the all-reduce and the read-back after it wait for the peers
+    double* out = nullptr;
+    TRY(resnorm_enqueue(c, level, &out));
     double h[2];
     HIP_TRY(c, hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->s));
     TRY(sync_and_check(c));
@@ -3142,6 +3167,164 @@ int mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean)
         L.fghost_ok = !L.p.dist;
     }
     if (level == 0) c->metrics_old = nullptr;  // psiOld and the metrics describe an iterate that is gone
+    return MGP_OK;
+}
+
+// ---- MAC-grid projection (mgp_project.hip's passes; the header has the definitions) ----
+
+// The caller's face arrays as device pointers for one call: device memory as it is, host memory through buffers
+// allocated here (uploaded when the call reads the faces) and freed when the call returns
+struct FaceArrays {
+    mgp_ctx* c;
+    void* host[3] = {nullptr, nullptr, nullptr};
+    char* dev[3] = {nullptr, nullptr, nullptr};
+    size_t bytes[3] = {0, 0, 0};
+    int axes = 0;
+    bool own = false;
+    explicit FaceArrays(mgp_ctx* cc) : c(cc) {}
+    ~FaceArrays()
+    {
+        if (own)
+            for (char* p : dev)
+                if (p) (void)hipFree(p);
+    }
+    int64_t reals(int a) const { return (int64_t)(bytes[a] / (size_t)c->rb); }
+    int open(void* vx, void* vy, void* vz, int mem, bool upload, const char* what)
+    {
+        const Level& L = c->lev[0];
+        const int64_t nx = L.p.nx, ny = L.p.ny, nz = L.g.nz;
+        axes = c->o.dim;
+        bytes[0] = (size_t)((nx + 1) * ny * nz) * c->rb;
+        bytes[1] = (size_t)(nx * (ny + 1) * nz) * c->rb;
+        bytes[2] = axes == 3 ? (size_t)(nx * ny * (nz + 1)) * c->rb : 0;
+        host[0] = vx, host[1] = vy, host[2] = axes == 3 ? vz : nullptr;
+        if (mem == MGP_MEM_DEVICE) {
+            for (int a = 0; a < axes; ++a) dev[a] = (char*)host[a];
+            return MGP_OK;
+        }
+        own = true;
+        for (int a = 0; a < axes; ++a)
+            if (hipMalloc(&dev[a], bytes[a]) != hipSuccess) {
+                dev[a] = nullptr;
+                (void)hipGetLastError();
+                return c->fail(MGP_ERR_OOM, "%s: no room for the device copies of the face arrays", what);
+            }
+        if (upload)
+            for (int a = 0; a < axes; ++a)
+                HIP_TRY(c, hipMemcpyAsync(dev[a], host[a], bytes[a], hipMemcpyHostToDevice, c->s));
+        return MGP_OK;
+    }
+    int download()
+    {
+        if (!own) return MGP_OK;
+        for (int a = 0; a < axes; ++a) HIP_TRY(c, hipMemcpyAsync(host[a], dev[a], bytes[a], hipMemcpyDeviceToHost, c->s));
+        return MGP_OK;
+    }
+};
+
+static int project_args(mgp_ctx* c, const char* what, const void* vx, const void* vy, const void* vz, int mem)
+{
+    if (!vx || !vy || (c->o.dim == 3 && !vz))
+        return c->fail(MGP_ERR_ARG, "%s: NULL face array (vx, vy%s)", what, c->o.dim == 3 ? ", vz" : "; vz is ignored in 2D");
+    if (mem != MGP_MEM_HOST && mem != MGP_MEM_DEVICE) return c->fail(MGP_ERR_ARG, "%s: unknown mem %d", what, mem);
+    return fmg_refuses(c, what);
+}
+
+// f of level 0 = D v; mgp_set_field(0, MGP_FIELD_F)'s state effects
+static int divergence_enqueue(mgp_ctx* c, const FaceArrays& v)
+{
+    Level& L = c->lev[0];
+    HIP_TRY(c, mgp::launch_divergence(c->rb, c->o.dim, v.dev[0], v.dev[1], v.dev[2], c->ui(L, L.f), L.g, c->s));
+    L.fghost_ok = !L.p.dist;
+    if (c->debug && c->d_dbg) {
+        const int id = (int)c->dbg_names.size();
+        c->dbg_names.push_back("mgp_divergence");
+        HIP_TRY(c, mgp::launch_nonfinite_check(c->rb, c->ui(L, L.f), L.g.P * L.g.nz, id, c->d_dbg, c->s));
+    }
+    return MGP_OK;
+}
+
+// faces = G psi or faces -= G psi, psi the one mgp_get_field(0, MGP_FIELD_U) returns
+static int gradient_enqueue(mgp_ctx* c, int op, const FaceArrays& v)
+{
+    Level& L = c->lev[0];
+    TRY(materialize_zero(c, L));
+    HIP_TRY(c, mgp::launch_gradient(c->rb, c->o.dim, op == MGP_GRAD_SUBTRACT, c->ui(L, L.u), v.dev[0], v.dev[1], v.dev[2],
+                                    L.g, coarse_coef(c->o.coarse_bc, 0), c->s));
+    if (c->debug && c->d_dbg)
+        for (int a = 0; a < v.axes; ++a) {
+            char name[48];
+            std::snprintf(name, sizeof name, "mgp_gradient, axis %d", a);
+            const int id = (int)c->dbg_names.size();
+            c->dbg_names.push_back(name);
+            HIP_TRY(c, mgp::launch_nonfinite_check(c->rb, v.dev[a], v.reals(a), id, c->d_dbg, c->s));
+        }
+    return MGP_OK;
+}
+
+int mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem)
+{
+    if (!c) return MGP_ERR_ARG;
+    TRY(project_args(c, "mgp_divergence", vx, vy, vz, mem));
+    FaceArrays v(c);
+    TRY(v.open(const_cast<void*>(vx), const_cast<void*>(vy), const_cast<void*>(vz), mem, true, "mgp_divergence"));
+    TRY(debug_reset(c));
+    TRY(divergence_enqueue(c, v));
+    TRY(sync_and_check(c));
+    return debug_verdict(c);
+}
+
+int mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (op != MGP_GRAD_STORE && op != MGP_GRAD_SUBTRACT) return c->fail(MGP_ERR_ARG, "mgp_gradient: unknown op %d", op);
+    TRY(project_args(c, "mgp_gradient", vx, vy, vz, mem));
+    FaceArrays v(c);
+    TRY(v.open(vx, vy, vz, mem, op == MGP_GRAD_SUBTRACT, "mgp_gradient"));
+    TRY(debug_reset(c));
+    TRY(gradient_enqueue(c, op, v));
+    TRY(v.download());
+    TRY(sync_and_check(c));
+    return debug_verdict(c);
+}
+
+int mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles, double norms[2])
+{
+    if (!c) return MGP_ERR_ARG;
+    if (fmg_cycles < 0 || cycles < 0) return c->fail(MGP_ERR_ARG, "mgp_project: fmg_cycles >= 0 and cycles >= 0");
+    TRY(project_args(c, "mgp_project", vx, vy, vz, mem));
+    if (fmg_cycles >= 1) TRY(fmg_check(c, fmg_cycles, cycles));
+    FaceArrays v(c);
+    TRY(v.open(vx, vy, vz, mem, true, "mgp_project"));
+    Level& L = c->lev[0];
+    TRY(debug_reset(c));
+    c->dbg_cycle = 0;
+    TRY(divergence_enqueue(c, v));
+    if (c->o.coarse_bc == MGP_BC_NEUMANN) {  // mgp_remove_mean(0, MGP_FIELD_F) without its read-back
+        if (!c->d_mean) HIP_TRY(c, hipMalloc(&c->d_mean, sizeof(double) * (mgp::kSumBlocks + 2)));
+        double* out = c->d_mean + mgp::kSumBlocks;
+        HIP_TRY(c, mgp::launch_mean_sum(c->rb, c->ui(L, L.f), L.g, c->d_mean, out, c->s));
+        HIP_TRY(c, mgp::launch_mean_sub(c->rb, c->ui(L, L.f), L.g, (double)c->ncells_global(), out, c->s));
+        c->metrics_old = nullptr;
+    }
+    if (fmg_cycles >= 1)
+        TRY(fmg_enqueue(c, fmg_cycles, cycles));
+    else
+        TRY(enqueue_cycles(c, cycles));
+    TRY(gradient_enqueue(c, MGP_GRAD_SUBTRACT, v));
+    TRY(v.download());
+    double h[2] = {0.0, 0.0};
+    if (norms) {
+        double* out = nullptr;
+        TRY(resnorm_enqueue(c, 0, &out));
+        HIP_TRY(c, hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, c->s));
+    }
+    TRY(sync_and_check(c));
+    TRY(debug_verdict(c));
+    if (norms) {
+        norms[0] = std::sqrt(h[1]);
+        norms[1] = std::sqrt(h[0]);
+    }
     return MGP_OK;
 }
 

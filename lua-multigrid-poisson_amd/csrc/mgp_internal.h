@@ -1,7 +1,7 @@
 // mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4 kernel units:
 // mgp_kernels.hip (one launch per piece; k_zs's stage-split variants and the 2D k_ys), mgp_zs.hip / mgp_zs_f64.hip (k_zs, the fused
 // phases' planning and dispatch), mgp_tail.hip (coarse tail), mgp_blk.hip / mgp_blk2.hip (tiled phases), mgp_gslex.hip,
-// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip, mgp_fmg.hip.  The last block holds what the kernel units
+// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip, mgp_fmg.hip, mgp_project.hip.  The last block holds what the kernel units
 // call in each other.  Not part of the public ABI (include/mgpoisson.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -209,6 +209,15 @@ hipError_t launch_refine_narrow(const double* src, float* dst, int64_t n, hipStr
 // the rows allow.
 hipError_t launch_mean_sum(int rb, const void* p, Geo g, double* partials, double* out, hipStream_t s);
 hipError_t launch_mean_sub(int rb, void* p, Geo g, double cells, double* out, hipStream_t s);
+
+// The operators of a MAC-grid projection (mgp_project.hip; mgp_divergence / mgp_gradient in include/mgpoisson.h have the
+// definitions).  rb = 4 / 8, one rank's whole box; f / u: interior plane 0 of level 0's packed f / psi (layout g); vx,
+// vy, vz: the caller's lexicographic face arrays in device memory ((nx+1) ny nz, nx (ny+1) nz, nx ny (nz+1) reals; vz
+// is not touched in 2D).  launch_divergence writes every cell of f and nothing else of it; launch_gradient stores G psi
+// into the faces or (subtract) subtracts it from them, with the ghosts -cl times the boundary cell.
+hipError_t launch_divergence(int rb, int dim, const void* vx, const void* vy, const void* vz, void* f, Geo g, hipStream_t s);
+hipError_t launch_gradient(int rb, int dim, bool subtract, const void* u, void* vx, void* vy, void* vz, Geo g, double cl,
+                           hipStream_t s);
 
 // Temporally blocked smoothing phases of a replicated 3D red/black level (ns = 2 sweeps):
 //   pre : dst = nu1 sweeps of src; R (coarse packed, Geo gc) = restrict(residual(dst))

@@ -104,6 +104,9 @@ int         mgp_remove_mean(mgp_ctx* c, int level, int which, double* mean);
 int         mgp_fmg_restrict_rhs(mgp_ctx* c, int level);
 int         mgp_fmg_prolong(mgp_ctx* c, int level);
 int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, double* errs);
+int         mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem);
+int         mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem);
+int         mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles, double norms[2]);
 int         mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean);
 int         mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean);
 int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
@@ -533,6 +536,44 @@ end
 -- the pieces of the full multigrid start: f of level + 1 = R f of level; u of level = P3 u of level + 1
 function MultigridHIP:fmgRestrictRhs(level) check(lib.mgp_fmg_restrict_rhs(self.ctx, level), self.ctx) end
 function MultigridHIP:fmgProlong(level) check(lib.mgp_fmg_prolong(self.ctx, level), self.ctx) end
+
+-- MAC-grid projection (this build's addition; include/mgpoisson.h has the definitions).  The face arrays are host
+-- buffers of the solver's real type (ffi.new(mg.ctype, count)), lexicographic with x fastest: vx (n+1) n [n], vy
+-- n (n+1) [n], vz n n (n+1) reals (3D only; nil in 2D); mg:faceCounts() returns the three counts.
+local function projectionCtx(self, what)
+	if rawget(self, 'group') then error(what .. ': single-GPU solvers only (ngpu > 1 runs mgp_group_*)', 3) end
+	if rawget(self, 'mixed') then error(what .. ": real = 'mixed' is not supported", 3) end
+	self:applyKnobs()
+	return self.ctx
+end
+
+function MultigridHIP:faceCounts()
+	local n = self.n
+	local nz = self.dim == 3 and n or 1
+	return (n + 1) * n * nz, n * (n + 1) * nz, self.dim == 3 and n * n * (nz + 1) or 0
+end
+
+-- f = D v (mgp_divergence)
+function MultigridHIP:divergence(vx, vy, vz)
+	local ctx = projectionCtx(self, 'divergence')
+	check(lib.mgp_divergence(ctx, vx, vy, vz, 0), ctx)
+end
+
+-- subtract ~= false: v -= G psi in place; subtract = false: the buffers receive G psi (mgp_gradient)
+function MultigridHIP:gradient(vx, vy, vz, subtract)
+	local ctx = projectionCtx(self, 'gradient')
+	check(lib.mgp_gradient(ctx, subtract == false and 0 or 1, vx, vy, vz, 0), ctx)
+end
+
+-- f = D v (its mean removed under boundary = 'neumann'), psi from a full multigrid start of `fmg` cycles per level and
+-- `cycles` final ones (fmg = 0: `cycles` outer iterations from the stored psi), v -= G psi in place (mgp_project).
+-- Returns ||D v||_2 before and after.
+function MultigridHIP:project(vx, vy, vz, fmg, cycles)
+	local ctx = projectionCtx(self, 'project')
+	local norms = ffi.new('double[2]')
+	check(lib.mgp_project(ctx, vx, vy, vz, 0, fmg or 1, cycles or 1, norms), ctx)
+	return norms[0], norms[1]
+end
 
 -- cpu-raw.lua:239-258 / gpu.lua:348-373: two outer iterations
 function MultigridHIP:run()

@@ -47,6 +47,7 @@ FIELD_RESIDUAL, FIELD_CORRECTION, FIELD_PSI_OLD, FIELD_ERROR, FIELD_TMP = 2, 3, 
 FIELDS = {"psi": FIELD_U, "f": FIELD_F, "Vs": FIELD_U, "Rs": FIELD_F, "rs": FIELD_RESIDUAL, "vs": FIELD_CORRECTION,
           "psiOld": FIELD_PSI_OLD, "errorBuf": FIELD_ERROR, "tmpU": FIELD_TMP}
 MEM_HOST, MEM_DEVICE = 0, 1
+GRAD_STORE, GRAD_SUBTRACT = 0, 1  # mgp_gradient's op
 # int fn(void* user, double h, void* u, const void* f, int64_t size)
 COARSE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                              ctypes.c_int64)
@@ -121,6 +122,9 @@ SIGNATURES = {
     "mgp_fmg_restrict_rhs": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mgp_fmg_prolong": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mgp_fmg": (ctypes.c_int, [_vp, _i32, _i32, _P(_dbl)]),
+    "mgp_divergence": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int]),
+    "mgp_gradient": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
+    "mgp_project": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _i32, _i32, _P(_dbl)]),
     "mgp_sync": (ctypes.c_int, [_vp]),
     "mgp_metrics": (ctypes.c_int, [_vp, _P(_dbl), _P(_i64), _P(_dbl)]),
     "mgp_set_coarse_level": (ctypes.c_int, [_vp, _i64]),

@@ -225,6 +225,70 @@ class Context:
         """u of level = the cubic prolongation of u of level + 1 (replaces u)."""
         self._chk(L.lib.mgp_fmg_prolong(self._h, int(level)))
 
+    # -- MAC-grid projection (mgp_divergence / mgp_gradient / mgp_project) --
+    def face_shapes(self):
+        """Shapes of the face arrays vx, vy, vz of level 0: (nz, ny, nx+1), (nz, ny+1, nx), (nz+1, ny, nx); 2D: nz = 1 and
+        no vz."""
+        lv = self.levels[0]
+        nx, ny, nz = lv["nx"], lv["ny"], (lv["nz_local"] if self.opts.dim == 3 else 1)
+        shapes = [(nz, ny, nx + 1), (nz, ny + 1, nx)]
+        if self.opts.dim == 3:
+            shapes.append((nz + 1, ny, nx))
+        return shapes
+
+    def _faces(self, vx, vy, vz, copy):
+        """The face arrays as C-contiguous arrays of the context's real type (new arrays when `copy`), shapes checked."""
+        shapes = self.face_shapes()
+        given = [vx, vy, vz][:len(shapes)]
+        out = []
+        for name, v, shape in zip("xyz", given, shapes):
+            if v is None:
+                raise ValueError(f"v{name} is required")
+            a = np.array(v, dtype=self.dtype, order="C") if copy else np.ascontiguousarray(v, dtype=self.dtype)
+            if a.shape != shape and not (self.opts.dim == 2 and a.shape == shape[1:]):
+                raise ValueError(f"v{name}: expected shape {shape}, got {a.shape}")
+            out.append(a)
+        return out
+
+    def _face_ptrs(self, faces):
+        return [a.ctypes.data for a in faces] + [None] * (3 - len(faces))
+
+    def divergence(self, vx, vy, vz=None):
+        """Level 0's f = the divergence of the staggered field (host arrays, see face_shapes)."""
+        self._chk(L.lib.mgp_divergence(self._h, *self._face_ptrs(self._faces(vx, vy, vz, False)), L.MEM_HOST))
+
+    def divergence_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, mem=L.MEM_DEVICE):
+        self._chk(L.lib.mgp_divergence(self._h, vx_ptr, vy_ptr, vz_ptr, mem))
+
+    def gradient(self, vx, vy, vz=None, subtract=True):
+        """New face arrays v - G psi (subtract) or G psi (then vx, vy, vz only give the shapes and may be None)."""
+        if not subtract:
+            vx, vy, vz = [np.zeros(s, dtype=self.dtype) for s in self.face_shapes()] + [None] * (3 - self.opts.dim)
+        faces = self._faces(vx, vy, vz, True)
+        op = L.GRAD_SUBTRACT if subtract else L.GRAD_STORE
+        self._chk(L.lib.mgp_gradient(self._h, op, *self._face_ptrs(faces), L.MEM_HOST))
+        return tuple(faces)
+
+    def gradient_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, subtract=True, mem=L.MEM_DEVICE):
+        op = L.GRAD_SUBTRACT if subtract else L.GRAD_STORE
+        self._chk(L.lib.mgp_gradient(self._h, op, vx_ptr, vy_ptr, vz_ptr, mem))
+
+    def project(self, vx, vy, vz=None, fmg=1, cycles=1):
+        """mgp_project on host arrays: (faces, (||D v||_2 before, after)) with faces the new projected arrays.  fmg >= 1:
+        a full multigrid start with `fmg` cycles per level and `cycles` final ones; fmg = 0: `cycles` outer iterations
+        from the stored psi."""
+        faces = self._faces(vx, vy, vz, True)
+        norms = (ctypes.c_double * 2)()
+        self._chk(L.lib.mgp_project(self._h, *self._face_ptrs(faces), L.MEM_HOST, int(fmg), int(cycles), norms))
+        return tuple(faces), (norms[0], norms[1])
+
+    def project_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, fmg=1, cycles=1, norms=True,
+                    mem=L.MEM_DEVICE):
+        """mgp_project on device pointers, in place; returns (before, after) or, with norms=False, None (no norm pass)."""
+        out = (ctypes.c_double * 2)() if norms else None
+        self._chk(L.lib.mgp_project(self._h, vx_ptr, vy_ptr, vz_ptr, mem, int(fmg), int(cycles), out))
+        return (out[0], out[1]) if norms else None
+
     def set_coarse_level(self, size: int):
         """Levels of nx <= size run in the one-launch LDS coarse engine (cpuDepth, cpu-gpu.lua:61)."""
         self._chk(L.lib.mgp_set_coarse_level(self._h, int(size)))

@@ -291,6 +291,29 @@ class MultigridHIP(_RawFields):
             print("err", err)
         return err
 
+    def _projection_ctx(self, what):
+        if self.mixed:
+            raise ValueError(f"{what}: real='mixed' is not supported (the projection operators run in the context's "
+                             "real type; use real='float' or 'double')")
+        self._ensure_ctx()
+        return self._ctx
+
+    def divergence(self, vx, vy, vz=None):
+        """f = the divergence of the staggered (MAC) field vx, vy[, vz] (this build's addition, mgp_divergence): host
+        arrays of shapes (nz, ny, nx+1), (nz, ny+1, nx), (nz+1, ny, nx); 2D: nz = 1 and no vz."""
+        self._projection_ctx("divergence").divergence(vx, vy, vz)
+
+    def gradient(self, vx, vy, vz=None, subtract=True):
+        """New face arrays v - G psi (``subtract``) or G psi, with the boundary's ghost rule (mgp_gradient)."""
+        return self._projection_ctx("gradient").gradient(vx, vy, vz, subtract)
+
+    def project(self, vx, vy, vz=None, fmg=1, cycles=1):
+        """Pressure projection / divergence cleaning in one call (mgp_project): f = D v (its mean removed under
+        boundary='neumann'), psi from a full multigrid start with ``fmg`` cycles per level and ``cycles`` final ones
+        (``fmg`` = 0: ``cycles`` outer iterations from the stored psi), v -= G psi.  Returns the new faces and
+        (div_before, div_after), the 2-norms of D v before and after."""
+        return self._projection_ctx("project").project(vx, vy, vz, fmg, cycles)
+
     def twoGrid(self, h, u, f):
         """cpu.lua:70 twoGrid(h, u, f): u updated in place.  u / f are (L, L[, L]) host arrays, or
         cpu.lua-style 1-based-indexed nested lists u[i][j] (x = i), whose rows are updated in place."""
