@@ -317,8 +317,10 @@ int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, 
  * Refused: NULL context, NULL vx or vy (vz in 3D), unknown mem or op, fmg_cycles < 0 or cycles < 0, an
  * MGP_ARITH_DOUBLE context: MGP_ERR_ARG; world > 1, loopback and group ranks, MGP_TRANSPORT=rccl ("single-GPU contexts
  * only") and active refinement: MGP_ERR_STATE; mgp_project with fmg_cycles >= 1: also whatever mgp_fmg refuses.
- * Limits: no batches (mgp_batch_*), no slab or group contexts, no mixed-precision refinement (real = 'mixed'), constant
- * density only, no cell-centred vector fields, and the wall value of the pressure is zero (face Dirichlet). */
+ * Limits: no batches (mgp_batch_*) through these three entry points: a batch has its own, mgp_batch_divergence,
+ * mgp_batch_gradient and mgp_batch_project below, with the same definitions per member; no slab or group contexts, no
+ * mixed-precision refinement (real = 'mixed'), constant density only, no cell-centred vector fields, and the wall value
+ * of the pressure is zero (face Dirichlet). */
 enum { MGP_GRAD_STORE = 0, MGP_GRAD_SUBTRACT = 1 };
 int         mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem);
 int         mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem);
@@ -492,6 +494,45 @@ int         mgp_batch_fmg_restrict_rhs(mgp_batch* b, int level);  /* every membe
 int         mgp_batch_fmg_prolong(mgp_batch* b, int level);       /* every member: u of level = P3 u of level+1 (replaces u) */
 int         mgp_batch_fmg(mgp_batch* b, int32_t cycles_per_level, int32_t final_cycles, double* errs);
 int         mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent);
+/* MAC-grid projection of the members: per member the definitions are those of mgp_divergence / mgp_gradient /
+ * mgp_project above (the same term order, every operation rounded in the real type T with no contraction, ih = (T)n[0],
+ * mc = -(T)c_0 with c_0 the level-0 boundary coefficient of the batch's coarse_bc, each ghost one multiplication that is
+ * always performed, a one-cell axis taking both ghosts from its one cell), so a member's f after mgp_batch_divergence
+ * and its faces after mgp_batch_gradient equal, bit for bit, what an ordinary context of the member's shape produces
+ * from the member's data.
+ * Face arrays: member slowest, then exactly the ordinary layout: vx[m][k][j][i] with (nx+1) ny nz reals per member, vy
+ * nx (ny+1) nz, vz nx ny (nz+1) (3D only; ignored and may be NULL in 2D); contiguous, owned by the caller, in host or
+ * device memory (mem), not overlapping.  member as in mgp_batch_set_field: >= 0 addresses one member and the arrays
+ * hold that member's faces, -1 all B members.  Host arrays go through device buffers allocated for the call
+ * (MGP_ERR_OOM if that fails, nothing stays allocated); device memory is the hot path.
+ * Each operator is ONE launch for any B and any member argument: its work is the flat list members x items (an item: 16
+ * bytes of each colour of a row, or one cell where rows are shorter than that or a pointer or member stride is not
+ * 16-byte aligned), so no workgroup is tied to one member and small members fill their workgroups.
+ * mgp_batch_divergence has the state effects of mgp_batch_set_field(member, 0, MGP_FIELD_F, ...): psi, psiOld and the
+ * stop state are untouched.  mgp_batch_gradient (op: MGP_GRAD_STORE / MGP_GRAD_SUBTRACT) reads the psi that
+ * mgp_batch_get_field(member, 0, MGP_FIELD_U, ...) returns and changes nothing in the batch.  Both act on stopped
+ * members too, as mgp_batch_remove_mean does, and synchronise once before returning.
+ * mgp_batch_project acts on all members, with one host synchronisation at the end (the first use of an fmg_cycles value
+ * adds the one mgp_batch_fmg documents):
+ *   1. f = D v on every member;
+ *   2. under MGP_BC_NEUMANN every member's f loses its own mean (mgp_batch_remove_mean's kernels and arithmetic);
+ *   3. fmg_cycles >= 1: mgp_batch_fmg(fmg_cycles, cycles)'s path (the captured ascent, the final iterations replaying
+ *      the cycle's graph, psiOld invalid after cycles = 0 as there); otherwise cycles >= 0 outer iterations from the
+ *      stored psi, mgp_batch_cycles' path (fmg_cycles = 0 and cycles = 0: psi stays as stored).  All members are armed:
+ *      a stop state left by mgp_batch_solve excludes nobody;
+ *   4. v -= G psi on every member.
+ * div_before / div_after (B doubles each; either may be NULL, both NULL skips the pass): ||f||_2 and ||f - A psi||_2
+ * per member, with the bits mgp_batch_residual_norm returns at that point (under Neumann "before" is the norm after
+ * the mean removal, as in mgp_project).
+ * MGP_ERR_ARG, with the entry point's name in mgp_batch_last_error: NULL vx or vy (vz in 3D) "NULL face array",
+ * "unknown mem", "unknown op", member outside [-1, B), fmg_cycles < 0 or cycles < 0; a NULL batch: MGP_ERR_ARG.
+ * Out of scope: a per-member stop inside the projection, variable density, cell-centred vector fields, a non-zero wall
+ * pressure, and a debug scan (batches have none).  Measured (tools/batch_project_time.py,
+ * profiles/batch_project_time.json): README "Batched MAC-grid projection". */
+int         mgp_batch_divergence(mgp_batch* b, int member, const void* vx, const void* vy, const void* vz, int mem);
+int         mgp_batch_gradient(mgp_batch* b, int member, int op, void* vx, void* vy, void* vz, int mem);
+int         mgp_batch_project(mgp_batch* b, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles,
+                              double* div_before, double* div_after);
 
 /* The reference's debugging check (MultigridCPURaw.debugging / MultigridGPU.debugging: show / showAndCheck after
  * every sweep and piece of twoGrid, error "found a nan" on a non-finite cell; cpu-raw.lua:126-140,

@@ -1320,8 +1320,9 @@ int field_io(mgp_batch* b, int member, int level, int which, void* buf, int64_t 
     return MGP_OK;
 }
 
-// k outer iterations of the armed members and the one synchronisation at the end (one more per full errs buffer)
-int cycles_armed(mgp_batch* b, int32_t k, double* errs)
+// k outer iterations of the armed members and the one synchronisation at the end (one more per full errs buffer);
+// sync = false (errs == nullptr): the caller enqueues more and synchronises itself
+int cycles_armed(mgp_batch* b, int32_t k, double* errs, bool sync = true)
 {
     if (k > 0) b->old_stale = false;
     for (int64_t done = 0; done < k;) {
@@ -1334,9 +1335,131 @@ int cycles_armed(mgp_batch* b, int32_t k, double* errs)
         if (done + n < k) BHIP(b, hipStreamSynchronize(b->s));  // (the errs buffer is reused by the next chunk)
         done += n;
     }
+    if (!sync) return MGP_OK;
     BHIP(b, hipStreamSynchronize(b->s));
     if (errs && !b->o.err_mode)
         for (int64_t i = 0; i < (int64_t)k * b->B; ++i) errs[i] = NAN;
+    return MGP_OK;
+}
+
+// d_norm[m] = sum (f - A u)^2, d_norm[B + m] = sum f^2 of member m on level 0 (mgp_batch_residual_norm's passes)
+int resnorm_enqueue(mgp_batch* b)
+{
+    const BHostLevel& L = b->lev[0];
+    const int nb = b->nbe;
+    const int64_t total = (int64_t)b->B * nb;
+    BTRY(dispatch(b, [&](auto t, auto d) {
+        using T = decltype(t);
+        constexpr int DIM = decltype(d)::value;
+        mgp::k_batch_resnorm<T, DIM><<<dim3((unsigned)total), dim3(kBlock), 0, b->s>>>((const T*)L.u, (const T*)L.f,
+                                                                                     dev_level<T, DIM>(L), nb, b->d_part);
+        BHIP(b, hipGetLastError());
+        return (int)MGP_OK;
+    }));
+    const unsigned g = (unsigned)((b->B + kBlock - 1) / kBlock);
+    mgp::k_batch_sum<<<dim3(g), dim3(kBlock), 0, b->s>>>(b->d_part, nb, b->B, b->d_norm);
+    BHIP(b, hipGetLastError());
+    mgp::k_batch_sum<<<dim3(g), dim3(kBlock), 0, b->s>>>(b->d_part + total, nb, b->B, b->d_norm + b->B);
+    BHIP(b, hipGetLastError());
+    return MGP_OK;
+}
+
+// every member's cells of a level's field lose the member's own mean; d_norm[B + m] = the mean (mgp_batch_remove_mean's
+// passes)
+int mean_enqueue(mgp_batch* b, const BHostLevel& L, char* base)
+{
+    const int nb = piece_blocks(L.slots);
+    const unsigned grid = (unsigned)((int64_t)b->B * nb);
+    if (b->rb == 4) {
+        mgp::k_batch_mean_sum<float><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const float*)base, L.g, L.slots,
+                                                                                     (double)L.cells, b->B, b->d_norm);
+        mgp::k_batch_mean_sub<float><<<dim3(grid), dim3(kBlock), 0, b->s>>>((float*)base, L.g, L.slots, nb, b->d_norm + b->B);
+    } else {
+        mgp::k_batch_mean_sum<double><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const double*)base, L.g, L.slots,
+                                                                                      (double)L.cells, b->B, b->d_norm);
+        mgp::k_batch_mean_sub<double><<<dim3(grid), dim3(kBlock), 0, b->s>>>((double*)base, L.g, L.slots, nb, b->d_norm + b->B);
+    }
+    BHIP(b, hipGetLastError());
+    return MGP_OK;
+}
+
+// ---- MAC-grid projection of the members (mgp_project.hip's k_div_b / k_grad_b; the header has the definitions) ----
+
+// The caller's face arrays of nm members as device pointers for one call: device memory as it is, host memory through
+// buffers allocated here (uploaded when the call reads the faces) and freed when the call returns
+struct BatchFaces {
+    mgp_batch* b;
+    void* host[3] = {nullptr, nullptr, nullptr};
+    char* dev[3] = {nullptr, nullptr, nullptr};
+    size_t bytes[3] = {0, 0, 0};
+    int axes = 0;
+    bool own = false;
+    explicit BatchFaces(mgp_batch* bb) : b(bb) {}
+    ~BatchFaces()
+    {
+        if (own)
+            for (char* p : dev)
+                if (p) (void)hipFree(p);
+    }
+    int open(void* vx, void* vy, void* vz, int mem, int nm, bool upload, const char* what)
+    {
+        const Geo& g = b->lev[0].g;
+        const size_t nx = (size_t)g.nx, ny = (size_t)g.ny, nz = (size_t)g.nz, per = (size_t)nm * b->rb;
+        axes = b->dim;
+        bytes[0] = (nx + 1) * ny * nz * per;
+        bytes[1] = nx * (ny + 1) * nz * per;
+        bytes[2] = axes == 3 ? nx * ny * (nz + 1) * per : 0;
+        host[0] = vx, host[1] = vy, host[2] = axes == 3 ? vz : nullptr;
+        if (mem == MGP_MEM_DEVICE) {
+            for (int a = 0; a < axes; ++a) dev[a] = (char*)host[a];
+            return MGP_OK;
+        }
+        own = true;
+        for (int a = 0; a < axes; ++a)
+            if (hipMalloc((void**)&dev[a], bytes[a]) != hipSuccess) {
+                dev[a] = nullptr;
+                (void)hipGetLastError();
+                return b->fail(MGP_ERR_OOM, "%s: no room for the device copies of the face arrays", what);
+            }
+        if (upload)
+            for (int a = 0; a < axes; ++a) BHIP(b, hipMemcpyAsync(dev[a], host[a], bytes[a], hipMemcpyHostToDevice, b->s));
+        return MGP_OK;
+    }
+    int download()
+    {
+        if (!own) return MGP_OK;
+        for (int a = 0; a < axes; ++a) BHIP(b, hipMemcpyAsync(host[a], dev[a], bytes[a], hipMemcpyDeviceToHost, b->s));
+        return MGP_OK;
+    }
+};
+
+int face_args(const mgp_batch* b, const char* what, int member, const void* vx, const void* vy, const void* vz, int mem)
+{
+    if (!vx || !vy || (b->dim == 3 && !vz))
+        return b->fail(MGP_ERR_ARG, "%s: NULL face array (vx, vy%s)", what, b->dim == 3 ? ", vz" : "; vz is ignored in 2D");
+    if (mem != MGP_MEM_HOST && mem != MGP_MEM_DEVICE) return b->fail(MGP_ERR_ARG, "%s: unknown mem %d", what, mem);
+    if (member < -1 || member >= b->B)
+        return b->fail(MGP_ERR_ARG, "%s: member %d out of range (batch %d)", what, member, b->B);
+    return MGP_OK;
+}
+
+// level 0's packed field `base` from member m0 on
+char* member_base(const mgp_batch* b, char* base, int m0) { return base + (size_t)m0 * b->lev[0].slots * b->rb; }
+
+// f of members [m0, m0 + nm) = D v
+int divergence_enqueue(mgp_batch* b, const BatchFaces& v, int m0, int nm)
+{
+    const BHostLevel& L = b->lev[0];
+    BHIP(b, mgp::launch_divergence_batch(b->rb, b->dim, v.dev[0], v.dev[1], v.dev[2], member_base(b, L.f, m0), L.g, nm, b->s));
+    return MGP_OK;
+}
+
+// faces = G psi or faces -= G psi of members [m0, m0 + nm)
+int gradient_enqueue(mgp_batch* b, int op, const BatchFaces& v, int m0, int nm)
+{
+    const BHostLevel& L = b->lev[0];
+    BHIP(b, mgp::launch_gradient_batch(b->rb, b->dim, op == MGP_GRAD_SUBTRACT, member_base(b, L.u, m0), v.dev[0], v.dev[1],
+                                       v.dev[2], L.g, L.cl, nm, b->s));
     return MGP_OK;
 }
 
@@ -1537,23 +1660,7 @@ int mgp_batch_solve(mgp_batch* b, double epsilon, int32_t maxiter, int32_t* iter
 int mgp_batch_residual_norm(mgp_batch* b, double* rnorm, double* fnorm)
 {
     if (!b) return MGP_ERR_ARG;
-    const BHostLevel& L = b->lev[0];
-    const int nb = b->nbe;
-    const int64_t total = (int64_t)b->B * nb;
-    const int rc = dispatch(b, [&](auto t, auto d) {
-        using T = decltype(t);
-        constexpr int DIM = decltype(d)::value;
-        mgp::k_batch_resnorm<T, DIM><<<dim3((unsigned)total), dim3(kBlock), 0, b->s>>>((const T*)L.u, (const T*)L.f,
-                                                                                     dev_level<T, DIM>(L), nb, b->d_part);
-        BHIP(b, hipGetLastError());
-        return (int)MGP_OK;
-    });
-    BTRY(rc);
-    const unsigned g = (unsigned)((b->B + kBlock - 1) / kBlock);
-    mgp::k_batch_sum<<<dim3(g), dim3(kBlock), 0, b->s>>>(b->d_part, nb, b->B, b->d_norm);
-    BHIP(b, hipGetLastError());
-    mgp::k_batch_sum<<<dim3(g), dim3(kBlock), 0, b->s>>>(b->d_part + total, nb, b->B, b->d_norm + b->B);
-    BHIP(b, hipGetLastError());
+    BTRY(resnorm_enqueue(b));
     std::vector<double> h(2 * (size_t)b->B);
     BHIP(b, hipMemcpyAsync(h.data(), b->d_norm, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b->s));
     BHIP(b, hipStreamSynchronize(b->s));
@@ -1571,19 +1678,7 @@ int mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means)
     if (which != MGP_FIELD_U && which != MGP_FIELD_F)
         return b->fail(MGP_ERR_ARG, "mgp_batch_remove_mean: which must be MGP_FIELD_U or MGP_FIELD_F");
     const BHostLevel& L = b->lev[level];
-    char* const base = which == MGP_FIELD_U ? L.u : L.f;
-    const int nb = piece_blocks(L.slots);
-    const unsigned grid = (unsigned)((int64_t)b->B * nb);
-    if (b->rb == 4) {
-        mgp::k_batch_mean_sum<float><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const float*)base, L.g, L.slots,
-                                                                                     (double)L.cells, b->B, b->d_norm);
-        mgp::k_batch_mean_sub<float><<<dim3(grid), dim3(kBlock), 0, b->s>>>((float*)base, L.g, L.slots, nb, b->d_norm + b->B);
-    } else {
-        mgp::k_batch_mean_sum<double><<<dim3((unsigned)b->B), dim3(kBlock), 0, b->s>>>((const double*)base, L.g, L.slots,
-                                                                                      (double)L.cells, b->B, b->d_norm);
-        mgp::k_batch_mean_sub<double><<<dim3(grid), dim3(kBlock), 0, b->s>>>((double*)base, L.g, L.slots, nb, b->d_norm + b->B);
-    }
-    BHIP(b, hipGetLastError());
+    BTRY(mean_enqueue(b, L, which == MGP_FIELD_U ? L.u : L.f));
     std::vector<double> h((size_t)b->B);
     BHIP(b, hipMemcpyAsync(h.data(), b->d_norm + b->B, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b->s));
     BHIP(b, hipStreamSynchronize(b->s));
@@ -1631,6 +1726,65 @@ int mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent)
 {
     if (!b || !ascent) return MGP_ERR_ARG;
     *ascent = b->fmg_launches;
+    return MGP_OK;
+}
+
+int mgp_batch_divergence(mgp_batch* b, int member, const void* vx, const void* vy, const void* vz, int mem)
+{
+    if (!b) return MGP_ERR_ARG;
+    BTRY(face_args(b, "mgp_batch_divergence", member, vx, vy, vz, mem));
+    const int m0 = member < 0 ? 0 : member, nm = member < 0 ? b->B : 1;
+    BatchFaces v(b);
+    BTRY(v.open(const_cast<void*>(vx), const_cast<void*>(vy), const_cast<void*>(vz), mem, nm, true, "mgp_batch_divergence"));
+    BTRY(divergence_enqueue(b, v, m0, nm));
+    BHIP(b, hipStreamSynchronize(b->s));
+    return MGP_OK;
+}
+
+int mgp_batch_gradient(mgp_batch* b, int member, int op, void* vx, void* vy, void* vz, int mem)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (op != MGP_GRAD_STORE && op != MGP_GRAD_SUBTRACT) return b->fail(MGP_ERR_ARG, "mgp_batch_gradient: unknown op %d", op);
+    BTRY(face_args(b, "mgp_batch_gradient", member, vx, vy, vz, mem));
+    const int m0 = member < 0 ? 0 : member, nm = member < 0 ? b->B : 1;
+    BatchFaces v(b);
+    BTRY(v.open(vx, vy, vz, mem, nm, op == MGP_GRAD_SUBTRACT, "mgp_batch_gradient"));
+    BTRY(gradient_enqueue(b, op, v, m0, nm));
+    BTRY(v.download());
+    BHIP(b, hipStreamSynchronize(b->s));
+    return MGP_OK;
+}
+
+int mgp_batch_project(mgp_batch* b, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles,
+                      double* div_before, double* div_after)
+{
+    if (!b) return MGP_ERR_ARG;
+    if (fmg_cycles < 0 || cycles < 0) return b->fail(MGP_ERR_ARG, "mgp_batch_project: fmg_cycles >= 0 and cycles >= 0");
+    BTRY(face_args(b, "mgp_batch_project", -1, vx, vy, vz, mem));
+    BatchFaces v(b);
+    BTRY(v.open(vx, vy, vz, mem, b->B, true, "mgp_batch_project"));
+    const BHostLevel& L = b->lev[0];
+    BTRY(divergence_enqueue(b, v, 0, b->B));
+    if (b->o.coarse_bc == MGP_BC_NEUMANN) BTRY(mean_enqueue(b, L, L.f));  // mgp_batch_remove_mean(0, F) without its read-back
+    BTRY(arm(b, 0, 0.0));
+    if (fmg_cycles >= 1) {  // mgp_batch_fmg's path
+        b->old_stale = true;
+        BTRY(enqueue_ascent(b, fmg_cycles));
+    }
+    BTRY(cycles_armed(b, cycles, nullptr, false));
+    BTRY(gradient_enqueue(b, MGP_GRAD_SUBTRACT, v, 0, b->B));
+    BTRY(v.download());
+    std::vector<double> h;
+    if (div_before || div_after) {
+        BTRY(resnorm_enqueue(b));
+        h.resize(2 * (size_t)b->B);
+        BHIP(b, hipMemcpyAsync(h.data(), b->d_norm, sizeof(double) * h.size(), hipMemcpyDeviceToHost, b->s));
+    }
+    BHIP(b, hipStreamSynchronize(b->s));
+    for (int m = 0; m < b->B && !h.empty(); ++m) {
+        if (div_before) div_before[m] = std::sqrt(h[b->B + m]);
+        if (div_after) div_after[m] = std::sqrt(h[m]);
+    }
     return MGP_OK;
 }
 

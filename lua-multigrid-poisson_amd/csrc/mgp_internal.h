@@ -218,6 +218,16 @@ hipError_t launch_mean_sub(int rb, void* p, Geo g, double cells, double* out, hi
 hipError_t launch_divergence(int rb, int dim, const void* vx, const void* vy, const void* vz, void* f, Geo g, hipStream_t s);
 hipError_t launch_gradient(int rb, int dim, bool subtract, const void* u, void* vx, void* vy, void* vz, Geo g, double cl,
                            hipStream_t s);
+// The same two on nm consecutive members of a batch (mgp_batch.hip) in ONE launch each: g is one member's box (z0 = 0,
+// P = 2 H, a power-of-two number of slots nz * P), f / u the first of those members' packed field (the next member
+// nz * P reals on), vx / vy / vz those members' face arrays, member slowest and contiguous ((nx+1) ny nz etc. reals per
+// member).  The vector form runs when launch_divergence's conditions hold for the first member and the member strides of
+// the packed field and of vy / vz are multiples of 16 bytes, the scalar form otherwise.  hipErrorInvalidValue: nm < 1 or
+// g is no member box.
+hipError_t launch_divergence_batch(int rb, int dim, const void* vx, const void* vy, const void* vz, void* f, Geo g, int nm,
+                                   hipStream_t s);
+hipError_t launch_gradient_batch(int rb, int dim, bool subtract, const void* u, void* vx, void* vy, void* vz, Geo g, double cl,
+                                 int nm, hipStream_t s);
 
 // Temporally blocked smoothing phases of a replicated 3D red/black level (ns = 2 sweeps):
 //   pre : dst = nu1 sweeps of src; R (coarse packed, Geo gc) = restrict(residual(dst))

@@ -145,6 +145,9 @@ int         mgp_batch_fmg_restrict_rhs(mgp_batch* b, int level);
 int         mgp_batch_fmg_prolong(mgp_batch* b, int level);
 int         mgp_batch_fmg(mgp_batch* b, int32_t cycles_per_level, int32_t final_cycles, double* errs);
 int         mgp_batch_fmg_launches(const mgp_batch* b, int64_t* ascent);
+int         mgp_batch_divergence(mgp_batch* b, int member, const void* vx, const void* vy, const void* vz, int mem);
+int         mgp_batch_gradient(mgp_batch* b, int member, int op, void* vx, void* vy, void* vz, int mem);
+int         mgp_batch_project(mgp_batch* b, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles, double* div_before, double* div_after);
 ]]
 
 local lib = ffi.load(os.getenv('MGP_LIBRARY') or 'mgpoisson')
@@ -724,6 +727,29 @@ function MGBatch:fmgLaunches()
 	local n = ffi.new('int64_t[1]')
 	checkBatch(lib.mgp_batch_fmg_launches(self.handle, n), self.handle)
 	return tonumber(n[0])
+end
+
+-- MAC-grid projection of the members (mgp_batch_divergence / mgp_batch_gradient / mgp_batch_project): raw real* host
+-- buffers, member slowest, then MultigridHIP:faceCounts() reals per member in MultigridHIP's layout (vz: 3D only, nil
+-- in 2D); member nil = every member, otherwise that member (0-based) and one member's faces
+
+-- every member's (or one member's) f = D v
+function MGBatch:divergence(vx, vy, vz, member)
+	checkBatch(lib.mgp_batch_divergence(self.handle, member or -1, vx, vy, vz, 0), self.handle)
+end
+
+-- subtract ~= false: v -= G psi in place; subtract = false: the buffers receive G psi
+function MGBatch:gradient(vx, vy, vz, subtract, member)
+	checkBatch(lib.mgp_batch_gradient(self.handle, member or -1, subtract == false and 0 or 1, vx, vy, vz, 0), self.handle)
+end
+
+-- MultigridHIP:project on every member in one call, in place: f = D v (each member's mean removed under boundary =
+-- 'neumann'), psi from mgp_batch_fmg's path (fmg = 0: `cycles` outer iterations from the stored psi), v -= G psi.
+-- Returns ||D v||_2 before and after per member (two double[batch])
+function MGBatch:project(vx, vy, vz, fmg, cycles)
+	local before, after = ffi.new('double[?]', self.batch), ffi.new('double[?]', self.batch)
+	checkBatch(lib.mgp_batch_project(self.handle, vx, vy, vz, 0, fmg or 1, cycles or 1, before, after), self.handle)
+	return before, after
 end
 
 MultigridHIP.Batch = MGBatch

@@ -177,6 +177,9 @@ SIGNATURES = {
     "mgp_batch_fmg_prolong": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mgp_batch_fmg": (ctypes.c_int, [_vp, _i32, _i32, _P(_dbl)]),
     "mgp_batch_fmg_launches": (ctypes.c_int, [_vp, _P(_i64)]),
+    "mgp_batch_divergence": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
+    "mgp_batch_gradient": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
+    "mgp_batch_project": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _i32, _i32, _P(_dbl), _P(_dbl)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -686,3 +686,86 @@ class BatchContext:
         n = ctypes.c_int64()
         self._chk(L.lib.mgp_batch_fmg_launches(self._h, ctypes.byref(n)))
         return n.value
+
+    # -- MAC-grid projection of the members (mgp_batch_divergence / mgp_batch_gradient / mgp_batch_project) --
+    def face_shapes(self, member=None):
+        """Shapes of the face arrays vx, vy, vz: (B, nz, ny, nx+1), (B, nz, ny+1, nx), (B, nz+1, ny, nx) for all members
+        (``member=None``), without the leading B for one member; 2D: nz = 1 and no vz."""
+        lv = self.levels[0]
+        nx, ny, nz = lv["nx"], lv["ny"], (lv["nz"] if self.opts.dim == 3 else 1)
+        lead = (self.batch,) if member is None else ()
+        shapes = [lead + (nz, ny, nx + 1), lead + (nz, ny + 1, nx)]
+        if self.opts.dim == 3:
+            shapes.append(lead + (nz + 1, ny, nx))
+        return shapes
+
+    def _faces(self, vx, vy, vz, member, copy):
+        """The face arrays as C-contiguous arrays of the batch's real type (new arrays when `copy`), shapes checked; a
+        2D array may come without its nz = 1 axis."""
+        shapes = self.face_shapes(member)
+        lead = 1 if member is None else 0
+        out = []
+        for name, v, shape in zip("xyz", [vx, vy, vz][:len(shapes)], shapes):
+            if v is None:
+                raise ValueError(f"v{name} is required")
+            a = np.array(v, dtype=self.dtype, order="C") if copy else np.ascontiguousarray(v, dtype=self.dtype)
+            flat2d = shape[:lead] + shape[lead + 1:]
+            if a.shape != shape and not (self.opts.dim == 2 and a.shape == flat2d):
+                raise ValueError(f"v{name}: expected shape {shape}, got {a.shape}")
+            out.append(a)
+        return out
+
+    @staticmethod
+    def _face_ptrs(faces):
+        return [a.ctypes.data for a in faces] + [None] * (3 - len(faces))
+
+    @staticmethod
+    def _member(member):
+        return -1 if member is None else int(member)
+
+    def divergence(self, vx, vy, vz=None, member=None):
+        """Level 0's f of every member (or of one) = the divergence of its staggered field (host arrays, see
+        face_shapes)."""
+        faces = self._faces(vx, vy, vz, member, False)
+        self._chk(L.lib.mgp_batch_divergence(self._h, self._member(member), *self._face_ptrs(faces), L.MEM_HOST))
+
+    def divergence_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, member=None, mem=L.MEM_DEVICE):
+        self._chk(L.lib.mgp_batch_divergence(self._h, self._member(member), vx_ptr, vy_ptr, vz_ptr, mem))
+
+    def gradient(self, vx, vy, vz=None, subtract=True, member=None):
+        """New face arrays v - G psi (subtract) or G psi (then vx, vy, vz only give the shapes and may be None)."""
+        if not subtract:
+            vx, vy, vz = [np.zeros(s, dtype=self.dtype) for s in self.face_shapes(member)] + [None] * (3 - self.opts.dim)
+        faces = self._faces(vx, vy, vz, member, True)
+        op = L.GRAD_SUBTRACT if subtract else L.GRAD_STORE
+        self._chk(L.lib.mgp_batch_gradient(self._h, self._member(member), op, *self._face_ptrs(faces), L.MEM_HOST))
+        return tuple(faces)
+
+    def gradient_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, subtract=True, member=None,
+                     mem=L.MEM_DEVICE):
+        op = L.GRAD_SUBTRACT if subtract else L.GRAD_STORE
+        self._chk(L.lib.mgp_batch_gradient(self._h, self._member(member), op, vx_ptr, vy_ptr, vz_ptr, mem))
+
+    def project(self, vx, vy, vz=None, fmg=1, cycles=1):
+        """mgp_batch_project on host arrays of all members: (faces, (before, after)) with faces the new projected arrays
+        and before / after the B values of ||D v||_2 per member.  fmg >= 1: a full multigrid start with `fmg` cycles per
+        level and `cycles` final ones; fmg = 0: `cycles` outer iterations from the stored psi."""
+        faces = self._faces(vx, vy, vz, None, True)
+        before = np.zeros(self.batch, dtype=np.float64)
+        after = np.zeros(self.batch, dtype=np.float64)
+        pd = ctypes.POINTER(ctypes.c_double)
+        self._chk(L.lib.mgp_batch_project(self._h, *self._face_ptrs(faces), L.MEM_HOST, int(fmg), int(cycles),
+                                          before.ctypes.data_as(pd), after.ctypes.data_as(pd)))
+        return tuple(faces), (before, after)
+
+    def project_ptr(self, vx_ptr: int, vy_ptr: int, vz_ptr: "int | None" = None, fmg=1, cycles=1, norms=True,
+                    mem=L.MEM_DEVICE):
+        """mgp_batch_project on device pointers, in place; returns (before, after), two arrays of B, or with norms=False
+        None (no norm pass)."""
+        pd = ctypes.POINTER(ctypes.c_double)
+        before = np.zeros(self.batch, dtype=np.float64) if norms else None
+        after = np.zeros(self.batch, dtype=np.float64) if norms else None
+        self._chk(L.lib.mgp_batch_project(self._h, vx_ptr, vy_ptr, vz_ptr, mem, int(fmg), int(cycles),
+                                          before.ctypes.data_as(pd) if norms else None,
+                                          after.ctypes.data_as(pd) if norms else None))
+        return (before, after) if norms else None

@@ -411,6 +411,21 @@ class MultigridHIPBatch:
             self.ctx.remove_mean(0, L.FIELD_U)
         return errs[-1].copy() if len(errs) else np.full(self.batch, np.nan)
 
+    def divergence(self, vx, vy, vz=None, member=None):
+        """Every member's f (or one member's) = the divergence of its staggered (MAC) field (mgp_batch_divergence): host
+        arrays of shapes (B, nz, ny, nx+1), (B, nz, ny+1, nx), (B, nz+1, ny, nx), without the B for one member; 2D:
+        nz = 1 and no vz."""
+        self.ctx.divergence(vx, vy, vz, member)
+
+    def gradient(self, vx, vy, vz=None, subtract=True, member=None):
+        """New face arrays v - G psi (``subtract``) or G psi per member (mgp_batch_gradient)."""
+        return self.ctx.gradient(vx, vy, vz, subtract, member)
+
+    def project(self, vx, vy, vz=None, fmg=1, cycles=1):
+        """``MultigridHIP.project`` on every member in one call (mgp_batch_project): returns the new faces and
+        (div_before, div_after), two arrays of B."""
+        return self.ctx.project(vx, vy, vz, fmg, cycles)
+
 
 def _smoother_name(v):
     if callable(v) and getattr(v, "__name__", "") in ("Jacobi", "GaussSeidel", "RedBlackGaussSeidel"):
