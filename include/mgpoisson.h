@@ -319,13 +319,69 @@ int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, 
  * only") and active refinement: MGP_ERR_STATE; mgp_project with fmg_cycles >= 1: also whatever mgp_fmg refuses.
  * Limits: no batches (mgp_batch_*) through these three entry points: a batch has its own, mgp_batch_divergence,
  * mgp_batch_gradient and mgp_batch_project below, with the same definitions per member; no slab or group contexts, no
- * mixed-precision refinement (real = 'mixed'), constant density only, no cell-centred vector fields, and the wall value
- * of the pressure is zero (face Dirichlet). */
+ * mixed-precision refinement (real = 'mixed'), no cell-centred vector fields, and the wall value of the pressure is
+ * zero (face Dirichlet).  Variable density: mgp_set_coefficients below (a context, not a batch). */
 enum { MGP_GRAD_STORE = 0, MGP_GRAD_SUBTRACT = 1 };
 int         mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem);
 int         mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem);
 int         mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles,
                         double norms[2]);
+
+/* Variable coefficients: div(beta grad psi) = f with positive coefficients beta on the cell faces (a two-phase or
+ * stratified flow's pressure equation div((dt / rho) grad p) = div v, electrostatics with a permittivity, Darcy flow).
+ * While a context has coefficients, every level of its cycle runs one launch per piece on kernels of their own
+ * (mgp_vc.hip), and the pieces, the norms and the projection use A_beta u = div(beta grad u).  A context that never
+ * sets coefficients is unchanged, and mgp_clear_coefficients returns a context to its engines and its bits.
+ *
+ * Definition.  T is the context's real type; every operation is rounded in T, without contraction.
+ * Face arrays: mgp_divergence's layout, one set per level l with that level's nx, ny, nz: bx[k][j][i], i in [0, nx], is
+ * beta on the x face between cells i - 1 and i; by has j in [0, ny]; bz has k in [0, nz] (3D only).
+ * Coarse coefficients: all axes halve together, as the hierarchy does.  A coarse face takes the arithmetic mean of the
+ * 2^(d-1) fine faces that tile it, the lower tangential axis fastest: the 3D x face (I, J, K) is
+ *   (((b(2I,2J,2K) + b(2I,2J+1,2K)) + b(2I,2J,2K+1)) + b(2I,2J+1,2K+1)) * (T)0.25,
+ * y faces over (x, z) and z faces over (x, y) in the same way; 2D: (b0 + b1) * (T)0.5.
+ * Operator: for cell (i, j, k) of level l, with its six face coefficients bxl, bxr, byl, byr, bzl, bzr (lower and upper
+ * face per axis), its neighbours' values xl .. zr (an out-of-box neighbour is the value +0), inv_hSq = 1 / h_l^2 (exact)
+ * and c = (T)c_l, the boundary coefficient of the level under the context's coarse_bc (all four values):
+ *   s      = ((((bxl xl + bxr xr) + byl yl) + byr yr) + bzl zl) + bzr zr       (2D: the first four terms)
+ *   S_all  = ((((bxl + bxr) + byl) + byr) + bzl) + bzr
+ *   S_wall = the same sum in the same order with every face that is not on the box replaced by +0
+ *   dg     = ((-S_all) - c S_wall) / hSq
+ *   relax:    a = f - s inv_hSq;  u = (dg == 0) ? +0 : RN(a / dg)     (IEEE division)
+ *   residual: r = f - (s inv_hSq + dg u)
+ * With beta = 1 everywhere this is the constant operator's arithmetic term for term (dg = ((T)(-2 dim) - nb c) / hSq), so
+ * a context with all-ones coefficients gives the constant context's bits under every boundary; the one-cell Neumann
+ * level has dg = 0 and relaxes to +0.  Restriction (the 2^d average in reduceResidual's order) and prolongation
+ * (piecewise constant or (tri)linear) are the constant cycle's kernels: they do not see beta.  Smoothing is red/black
+ * Gauss-Seidel with nu1 / nu2; V and F cycles, fresh and warm guesses and coarse_sweeps all apply; err / psiOld as in
+ * the per-piece cycle.
+ * Gradient with coefficients: g as defined for mgp_gradient; MGP_GRAD_STORE writes beta_face g, MGP_GRAD_SUBTRACT
+ * v - (beta_face g), the product rounded first.  In exact arithmetic D (v - beta G psi) = f - A_beta psi, wall faces
+ * included (their term is beta_w (1 + c_0) psi / h^2), so mgp_project with fmg_cycles = 0 is the variable-density
+ * projection and its norms are {||f||, ||f - A_beta psi||}.  mgp_divergence is unchanged.
+ *
+ * mgp_set_coefficients reads level 0's faces from host or device memory (bz is ignored in 2D), checks on the device
+ * that every value is finite and > 0 (otherwise MGP_ERR_ARG, "coefficient not positive and finite: axis a", and the
+ * context is exactly as before the call: earlier coefficients, if any, stay in force), builds every level's coefficients
+ * (one launch per level and axis), drops the captured cycle graphs (re-captured on first use) and synchronises once.
+ * MGP_ERR_OOM leaves the context unchanged.  Setting again replaces the coefficients.  mgp_get_coefficients returns
+ * any level's array of `axis` (0 x, 1 y, 2 z) in the face layout; count = its number of reals; MGP_ERR_STATE when none
+ * are set.  While coefficients are set mgp_level_info reports engine 0 on every level, and mgp_cycle(s), mgp_smooth,
+ * mgp_residual_restrict, mgp_prolong_correct, mgp_coarse_solve, mgp_residual_norm, mgp_get_field(MGP_FIELD_RESIDUAL /
+ * _CORRECTION), mgp_metrics, mgp_remove_mean (unchanged: A_beta keeps the constant null space, so Neumann still needs
+ * sum f = 0) and mgp_set_debug follow beta.
+ * Refused by mgp_set_coefficients, MGP_ERR_ARG: an MGP_ARITH_DOUBLE context, a smoother other than MGP_RBGS,
+ * MGP_RESTRICT_FULL_WEIGHTING, a NULL array, an unknown mem; MGP_ERR_STATE: world > 1, loopback and group ranks,
+ * MGP_TRANSPORT=rccl ("single-GPU contexts only"), active refinement, a coarse hand-off that is set.  Refused with
+ * MGP_ERR_STATE while coefficients are set: mgp_two_grid, mgp_cg_solve, mgp_fmg, mgp_fmg_restrict_rhs, mgp_fmg_prolong,
+ * mgp_project with fmg_cycles >= 1 (before f is written), mgp_refine_begin, mgp_set_coarse_handoff with a function,
+ * mgp_set_coarse_level with size > 0.
+ * Limits: no batches, slabs, full multigrid start, refinement, Jacobi or lexicographic Gauss-Seidel with coefficients.
+ * Sharp coefficient jumps slow the plain cycle down (the README has figures); a Krylov wrapper is future work. */
+int         mgp_set_coefficients(mgp_ctx* c, const void* bx, const void* by, const void* bz, int mem);
+int         mgp_clear_coefficients(mgp_ctx* c);
+int         mgp_has_coefficients(const mgp_ctx* c);                 /* 0 / 1 */
+int         mgp_get_coefficients(const mgp_ctx* c, int level, int axis, void* dst, int64_t count, int mem);
 
 /* The reference's Krylov cross-check (test/converge-multigrid-vs-krylov.lua:38-69, solver.conjgrad) on
  * the device, as an independent second oracle for the converged multigrid answer: matrix-free

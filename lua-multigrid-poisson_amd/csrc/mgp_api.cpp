@@ -168,6 +168,12 @@ struct Level {
     int64_t exchanges = 0;      // halo exchanges of this level so far (mgp_level_info info[7])
     bool early_u = false;       // POST's u halo was exchanged on the side stream after PRE (wait on x_ev1)
     int zc = 0, zc_pre = 0;  // k_zs z-chunks (planes per workgroup) of POST and PRE
+    // face coefficients (mgp_set_coefficients; mgp_vc.hip has the layout): per axis the lower faces in the level's packed
+    // layout (allocated like u), and the faces of the upper x and y walls
+    char* vb[3] = {nullptr, nullptr, nullptr};
+    char* vwx = nullptr;
+    char* vwy = nullptr;
+    bool sv_fused = false, sv_blk = false, sv_zpost = false, sv_zpre = false;  // the engines to return to when cleared
 };
 
 // Loopback transport (tests): the ranks of a slab decomposition as contexts of one process on
@@ -280,6 +286,12 @@ struct mgp_ctx {
     char* f64 = nullptr;
     double* d_ref = nullptr;
     bool refining() const { return psi64 != nullptr; }
+    // Face coefficients are set (mgp_set_coefficients): every level runs one launch per piece on mgp_vc.hip's kernels.
+    // The engine choices of select_engines are saved (sv_*, Level::sv_*) and put back by mgp_clear_coefficients.
+    bool vc = false;
+    int sv_tail_level = -1;
+    bool sv_fresh = false, sv_lazy = false, sv_bres = false, sv_post1 = false, sv_rbsweep = false;
+    int* d_vcbad = nullptr;  // the validation pass's flag bits (one per axis)
     std::map<char*, char*> pad_base;  // (MGP_PAD_BYTES) offset pointer -> its allocation
     size_t pad = 0;                   // MGP_PAD_BYTES at creation
     int64_t part_cap = 0;
@@ -793,6 +805,16 @@ int64_t level_count(const Level& L) { return L.p.nx * L.p.ny * (L.g.nz); }
 
 int materialize_zero(mgp_ctx* c, Level& L);
 
+// a level's coefficients as the kernels take them (pointers to interior plane 0)
+mgp::VcCoef vc_of(const mgp_ctx* c, const Level& L)
+{
+    mgp::VcCoef v;
+    for (int a = 0; a < 3; ++a) v.b[a] = L.vb[a] ? c->ui(L, L.vb[a]) : nullptr;
+    v.wx = L.vwx;
+    v.wy = L.vwy;
+    return v;
+}
+
 // One half-sweep (colour `color`) reading `other`, writing `dst`; level-0 launches are timed.
 // lo / hi > 0: the slab extended by that many ghost planes below / above (deep-halo smoothing).
 int half(mgp_ctx* c, int l, int color, char* other, char* dst, const char* old, double h, double cl, int part_off,
@@ -810,6 +832,12 @@ int half(mgp_ctx* c, int l, int color, char* other, char* dst, const char* old, 
     // matches that kernel's rocprofv3 row; the err-fused variant reads psiOld as well
     hipEvent_t e;
     TRY(timed_begin(c, old ? -1 : l, &e));
+    if (c->vc) {  // (one rank's whole box: no extended slab)
+        HIP_TRY(c, mgp::launch_half_sweep_vc(c->rb, c->o.dim, color, c->ui(L, other), c->ui(L, L.f), c->ui(L, dst),
+                                             old ? c->ui(L, (char*)old) : nullptr, c->d_part + part_off, g, h, cl,
+                                             vc_of(c, L), c->s));
+        return timed_end(c, e, MGP_TIMING_HALF_SWEEP, (c->o.dim == 3 ? 4.5 : 3.5) * c->rb * (double)level_cells(L));
+    }
     HIP_TRY(c, mgp::launch_half_sweep(c->rk, c->o.dim, l == 0, color, c->ui(L, other) - back, c->ui(L, L.f) - back,
                                       c->ui(L, dst) - back, old ? c->ui(L, (char*)old) : nullptr, c->d_part + part_off,
                                       g, h, cl, c->use_gs, c->pt, c->s));
@@ -907,7 +935,7 @@ int smooth(mgp_ctx* c, int l, int sweeps, double h, bool want_err = false, bool 
             continue;
         }
         const char* old = last_err ? L.t : nullptr;
-        const int nb = mgp::half_blocks(c->rk, L.g, c->use_gs);
+        const int nb = c->vc ? mgp::half_blocks_vc(c->rb, L.g) : mgp::half_blocks(c->rk, L.g, c->use_gs);
         char* dst = oop ? L.t : L.u;
         if (!(red_done && sw == 0)) {
             TRY(exchange(c, L));
@@ -1065,6 +1093,12 @@ int residual_restrict(mgp_ctx* c, int l, double h)
     int64_t zc = 0;
     const Geo gc = coarse_view(L, C, &zc);
     char* R = c->ui(C, C.f) + (size_t)(zc * C.g.P) * c->rb;
+    if (c->vc) {
+        HIP_TRY(c, mgp::launch_residual_restrict_vc(c->rb, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), R, L.g, gc, h,
+                                                    coarse_coef(c->o.coarse_bc, l), vc_of(c, L), c->pt, c->s));
+        C.fghost_ok = true;
+        return MGP_OK;
+    }
     HIP_TRY(c, mgp::launch_residual_restrict(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), R, L.g, gc, h,
                                              coarse_coef(c->o.coarse_bc, l), c->pt, c->s));
     C.fghost_ok = !C.p.dist;
@@ -2109,6 +2143,14 @@ int mgp_plan_comm(const mgp_opts* o, int32_t cycles, int64_t* rows, int max_rows
     return mgp_comm_log(&c, rows, max_rows, 0);
 }
 
+static void vc_free(Level& L)
+{
+    for (char** p : {&L.vb[0], &L.vb[1], &L.vb[2], &L.vwx, &L.vwy}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+}
+
 static void destroy_impl(mgp_ctx* c)
 {
     if (!c) return;
@@ -2118,7 +2160,9 @@ static void destroy_impl(mgp_ctx* c)
         if (L.u) dev_free(c, L.u);
         if (L.f) dev_free(c, L.f);
         if (L.t) dev_free(c, L.t);
+        vc_free(L);
     }
+    if (c->d_vcbad) (void)hipFree(c->d_vcbad);
     if (c->zbuf) (void)hipFree(c->zbuf);
     if (c->psi_old) (void)hipFree(c->psi_old);
     if (c->rscratch) (void)hipFree(c->rscratch);
@@ -2264,6 +2308,7 @@ static void select_engines(mgp_ctx* c)
 static int level_engine(const mgp_ctx* c, int l)
 {
     const Level& L = c->lev[l];
+    if (c->vc) return 0;
     return c->tail_level >= 0 && l >= c->tail_level ? 1 : L.fused ? 2 : L.blk ? 3 : L.zpost ? 4 : 0;
 }
 
@@ -2496,6 +2541,14 @@ static int refine_refuses(mgp_ctx* c, const char* what)
                                   "the scratch of its inner solve; use mgp_refine_* or call mgp_refine_end first", what);
 }
 
+// While face coefficients are set the cycle is the per-piece one on A_beta: what runs other engines or another operator
+// is refused
+static int vc_refuses(mgp_ctx* c, const char* what)
+{
+    return c->fail(MGP_ERR_STATE, "%s: not while face coefficients are set (mgp_set_coefficients); call "
+                                  "mgp_clear_coefficients first", what);
+}
+
 // interior plane 0 of a level-0-shaped fp64 field
 static double* ui64(const mgp_ctx* c, char* base) { return (double*)(base + (size_t)(c->G * c->lev[0].g.P) * 8); }
 
@@ -2553,6 +2606,11 @@ static int field_source(mgp_ctx* c, int level, int which, char** src, char** scr
         HIP_TRY(c, mgp::launch_sqdiff_field(c->rk, c->ui(L, L.u), c->metrics_old, sc, n, c->s));
     } else if (which == MGP_FIELD_RESIDUAL) {
         TRY(exchange(c, L));
+        if (c->vc)
+            HIP_TRY(c, mgp::launch_residual_field_vc(c->rb, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), sc, L.g,
+                                                     level_h(c, level), coarse_coef(c->o.coarse_bc, level), vc_of(c, L),
+                                                     c->s));
+        else
         HIP_TRY(c, mgp::launch_residual_field(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), sc, L.g, level_h(c, level),
                                               coarse_coef(c->o.coarse_bc, level), c->s));
     } else {  // MGP_FIELD_CORRECTION: P V onto zeros
@@ -2803,6 +2861,7 @@ int mgp_two_grid(mgp_ctx* c, double h, void* u, const void* f, int64_t L, int me
 {
     if (!c || !u || !f) return MGP_ERR_ARG;
     if (c->refining()) return refine_refuses(c, "mgp_two_grid");
+    if (c->vc) return vc_refuses(c, "mgp_two_grid");
     if (c->o.world > 1) return c->fail(MGP_ERR_STATE, "mgp_two_grid: single-GPU contexts only");
     for (int l = 0; l < (int)c->lev.size(); ++l) {
         Level& Lv = c->lev[l];
@@ -2935,6 +2994,7 @@ int mgp_fmg_restrict_rhs(mgp_ctx* c, int level)
     if (!c) return MGP_ERR_ARG;
     if (level < 0 || level + 1 >= (int)c->lev.size()) return c->fail(MGP_ERR_ARG, "mgp_fmg_restrict_rhs: bad level %d", level);
     TRY(fmg_refuses(c, "mgp_fmg_restrict_rhs"));
+    if (c->vc) return vc_refuses(c, "mgp_fmg_restrict_rhs");
     TRY(debug_reset(c));
     c->dbg_cycle = 0;
     TRY(fmg_restrict_rhs(c, level));
@@ -2947,6 +3007,7 @@ int mgp_fmg_prolong(mgp_ctx* c, int level)
     if (!c) return MGP_ERR_ARG;
     if (level < 0 || level + 1 >= (int)c->lev.size()) return c->fail(MGP_ERR_ARG, "mgp_fmg_prolong: bad level %d", level);
     TRY(fmg_refuses(c, "mgp_fmg_prolong"));
+    if (c->vc) return vc_refuses(c, "mgp_fmg_prolong");
     TRY(debug_reset(c));
     c->dbg_cycle = 0;
     TRY(fmg_prolong(c, level));
@@ -2961,6 +3022,7 @@ static int fmg_check(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles)
     if (cycles_per_level < 1 || final_cycles < 0)
         return c->fail(MGP_ERR_ARG, "mgp_fmg: cycles_per_level >= 1 and final_cycles >= 0");
     TRY(fmg_refuses(c, "mgp_fmg"));
+    if (c->vc) return vc_refuses(c, "mgp_fmg");
     if (c->handoff_fn) return c->fail(MGP_ERR_STATE, "mgp_fmg: a coarse hand-off is set (mgp_set_coarse_handoff)");
     return MGP_OK;
 }
@@ -3011,9 +3073,11 @@ static int level_of_size(const mgp_ctx* c, int64_t size)
 int mgp_set_coarse_level(mgp_ctx* c, int64_t size)
 {
     if (!c) return MGP_ERR_ARG;
+    if (c->vc && size > 0) return vc_refuses(c, "mgp_set_coarse_level");
     TRY(sync_and_check(c));
     drop_graphs(c);
     if (size == 0) {
+        c->sv_tail_level = -1;  // (with coefficients set: the engine choice mgp_clear_coefficients returns to)
         c->tail_level = -1;
         return ensure_rscratch(c, true);  // the former tail levels now restrict per piece
     }
@@ -3034,6 +3098,7 @@ int mgp_set_coarse_level(mgp_ctx* c, int64_t size)
 int mgp_set_coarse_handoff(mgp_ctx* c, int64_t size, mgp_coarse_fn fn, void* user)
 {
     if (!c) return MGP_ERR_ARG;
+    if (c->vc) return fn ? vc_refuses(c, "mgp_set_coarse_handoff") : MGP_OK;  // (none can be set with coefficients)
     TRY(sync_and_check(c));
     drop_graphs(c);
     if (!fn) {
@@ -3088,7 +3153,7 @@ static int resnorm_enqueue(mgp_ctx* c, int level, double** res)
     Level& L = c->lev[level];
     TRY(materialize_zero(c, L));
     TRY(exchange(c, L));
-    const int nb = mgp::resnorm_blocks(c->rk, L.g);
+    const int nb = c->vc ? mgp::resnorm_blocks_vc(L.g) : mgp::resnorm_blocks(c->rk, L.g);
     const int64_t need = 2 * (int64_t)(nb + mgp::sum_scratch(nb)) + 2;
     if (need > c->d_rn_cap) {
         if (c->d_rn) HIP_TRY(c, hipFree(c->d_rn));
@@ -3098,6 +3163,10 @@ static int resnorm_enqueue(mgp_ctx* c, int level, double** res)
         c->d_rn_cap = need;
     }
     double* out = c->d_rn + need - 2;
+    if (c->vc)
+        HIP_TRY(c, mgp::launch_residual_norm_vc(c->rb, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), L.g, level_h(c, level),
+                                                coarse_coef(c->o.coarse_bc, level), vc_of(c, L), c->d_rn, out, c->s));
+    else
     HIP_TRY(c, mgp::launch_residual_norm(c->rk, c->o.dim, c->ui(L, L.u), c->ui(L, L.f), L.g, level_h(c, level),
                                          coarse_coef(c->o.coarse_bc, level), c->d_rn, out, c->s));
     WaitScope w(c);  // the all-reduce and the read-back after it wait for the peers
@@ -3249,6 +3318,10 @@ static int gradient_enqueue(mgp_ctx* c, int op, const FaceArrays& v)
 {
     Level& L = c->lev[0];
     TRY(materialize_zero(c, L));
+    if (c->vc)
+        HIP_TRY(c, mgp::launch_gradient_vc(c->rb, c->o.dim, op == MGP_GRAD_SUBTRACT, c->ui(L, L.u), v.dev[0], v.dev[1],
+                                           v.dev[2], L.g, coarse_coef(c->o.coarse_bc, 0), vc_of(c, L), c->s));
+    else
     HIP_TRY(c, mgp::launch_gradient(c->rb, c->o.dim, op == MGP_GRAD_SUBTRACT, c->ui(L, L.u), v.dev[0], v.dev[1], v.dev[2],
                                     L.g, coarse_coef(c->o.coarse_bc, 0), c->s));
     if (c->debug && c->d_dbg)
@@ -3328,6 +3401,170 @@ int mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_c
     return MGP_OK;
 }
 
+// ---- face coefficients: A_beta u = div(beta grad u) (mgp_vc.hip's kernels; the header has the definition) ----
+
+// every level one launch per piece on the coefficient kernels (on), or select_engines' choices again (off)
+static void vc_engines(mgp_ctx* c, bool on)
+{
+    if (on == c->vc) return;
+    if (on) {
+        for (auto& L : c->lev) {
+            L.sv_fused = L.fused, L.sv_blk = L.blk, L.sv_zpost = L.zpost, L.sv_zpre = L.zpre;
+            L.fused = L.blk = L.zpost = L.zpre = false;
+        }
+        c->sv_tail_level = c->tail_level;
+        c->sv_fresh = c->fresh_sweep, c->sv_lazy = c->lazy_zero, c->sv_bres = c->bres, c->sv_post1 = c->post1;
+        c->sv_rbsweep = c->rbsweep;
+        c->tail_level = -1;
+        // (fresh coarse guesses are real zeros: the coefficient kernels always load the guess)
+        c->fresh_sweep = c->lazy_zero = c->bres = c->post1 = c->rbsweep = false;
+    } else {
+        for (auto& L : c->lev) L.fused = L.sv_fused, L.blk = L.sv_blk, L.zpost = L.sv_zpost, L.zpre = L.sv_zpre;
+        c->tail_level = c->sv_tail_level;
+        c->fresh_sweep = c->sv_fresh, c->lazy_zero = c->sv_lazy, c->bres = c->sv_bres, c->post1 = c->sv_post1;
+        c->rbsweep = c->sv_rbsweep;
+    }
+    c->vc = on;
+}
+
+int mgp_has_coefficients(const mgp_ctx* c) { return c ? (c->vc ? 1 : 0) : MGP_ERR_ARG; }
+
+int mgp_set_coefficients(mgp_ctx* c, const void* bx, const void* by, const void* bz, int mem)
+{
+    if (!c) return MGP_ERR_ARG;
+    const char* what = "mgp_set_coefficients";
+    if (c->rk == mgp::kRealF32D)
+        return c->fail(MGP_ERR_ARG, "%s: the coefficient kernels evaluate in the real type; arith = MGP_ARITH_DOUBLE is "
+                                    "not supported", what);
+    if (c->o.smoother != MGP_RBGS) return c->fail(MGP_ERR_ARG, "%s: the red/black Gauss-Seidel smoother only", what);
+    if (c->o.restriction == MGP_RESTRICT_FULL_WEIGHTING)
+        return c->fail(MGP_ERR_ARG, "%s: the average restriction only (not MGP_RESTRICT_FULL_WEIGHTING)", what);
+    if (!bx || !by || (c->o.dim == 3 && !bz))
+        return c->fail(MGP_ERR_ARG, "%s: NULL coefficient array (bx, by%s)", what, c->o.dim == 3 ? ", bz" : "; bz is ignored in 2D");
+    if (mem != MGP_MEM_HOST && mem != MGP_MEM_DEVICE) return c->fail(MGP_ERR_ARG, "%s: unknown mem %d", what, mem);
+    if (c->multi() || c->lb || c->group_stop || c->nb_comm) return c->fail(MGP_ERR_STATE, "%s: single-GPU contexts only", what);
+    if (c->refining()) return refine_refuses(c, what);
+    if (c->handoff_fn) return c->fail(MGP_ERR_STATE, "%s: a coarse hand-off is set (mgp_set_coarse_handoff)", what);
+    const int dim = c->o.dim;
+    const size_t rb = (size_t)c->rb;
+    // everything that can fail for lack of memory comes first: the context stays as it is
+    if (!c->d_vcbad && hipMalloc(&c->d_vcbad, sizeof(int)) != hipSuccess) {
+        c->d_vcbad = nullptr;
+        return c->fail(MGP_ERR_OOM, "%s: no room for the validation flag", what);
+    }
+    {
+        // the err partials of the per-piece half-sweeps on level 0
+        const int nb2 = 2 * mgp::half_blocks_vc(c->rb, c->lev[0].g);
+        const int64_t need = std::max<int64_t>(mgp::kSumBlocks, nb2 + mgp::sum_scratch(nb2));
+        if (need > c->part_cap) {
+            double* p = nullptr;
+            if (hipMalloc(&p, sizeof(double) * need) != hipSuccess) return c->fail(MGP_ERR_OOM, "%s: no room for the err partials", what);
+            TRY(sync_and_check(c));
+            drop_graphs(c);  // (they write into the old buffer)
+            (void)hipFree(c->d_part);
+            c->d_part = p;
+            c->part_cap = need;
+        }
+    }
+    FaceArrays v(c);
+    TRY(v.open(const_cast<void*>(bx), const_cast<void*>(by), const_cast<void*>(bz), mem, true, what));
+    std::vector<Level> nw(c->lev.size());  // (only the coefficient pointers are used)
+    auto release = [&] {
+        for (auto& L : nw) vc_free(L);
+    };
+    for (size_t l = 0; l < c->lev.size(); ++l) {
+        const Level& L = c->lev[l];
+        const size_t bytes = (size_t)L.alloc * rb;
+        const size_t wxb = (size_t)(L.g.ny * L.g.nz) * rb, wyb = (size_t)(2 * L.g.hw * L.g.nz) * rb;
+        bool ok = hipMalloc(&nw[l].vwx, wxb) == hipSuccess && hipMalloc(&nw[l].vwy, wyb) == hipSuccess;
+        for (int a = 0; a < dim && ok; ++a)
+            ok = hipMalloc(&nw[l].vb[a], bytes) == hipSuccess && hipMemsetAsync(nw[l].vb[a], 0, bytes, c->s) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(c->s);
+            release();
+            return c->fail(MGP_ERR_OOM, "%s: no room for the coefficients of level %d", what, (int)l);
+        }
+    }
+    auto view = [&](size_t l) {
+        Level t = c->lev[l];
+        for (int a = 0; a < 3; ++a) t.vb[a] = nw[l].vb[a];
+        t.vwx = nw[l].vwx, t.vwy = nw[l].vwy;
+        return vc_of(c, t);
+    };
+    // one validation pass over the raw input, then one launch per level and axis into the new arrays; one
+    // synchronisation decides whether they replace the context's
+    int rc = MGP_OK;
+    auto step = [&](hipError_t e) {
+        if (rc == MGP_OK && e != hipSuccess) rc = c->fail(MGP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    };
+    step(hipMemsetAsync(c->d_vcbad, 0, sizeof(int), c->s));
+    for (int a = 0; a < dim; ++a) step(mgp::launch_vc_check(c->rb, v.dev[a], v.reals(a), c->d_vcbad, 1 << a, c->s));
+    for (int a = 0; a < dim; ++a) step(mgp::launch_vc_pack(c->rb, dim, a, v.dev[a], view(0), c->lev[0].g, c->s));
+    for (size_t l = 0; l + 1 < c->lev.size(); ++l)
+        for (int a = 0; a < dim; ++a)
+            step(mgp::launch_vc_coarsen(c->rb, dim, a, view(l), c->lev[l].g, view(l + 1), c->lev[l + 1].g, c->s));
+    int bad = 0;
+    step(hipMemcpyAsync(&bad, c->d_vcbad, sizeof(int), hipMemcpyDeviceToHost, c->s));
+    if (rc == MGP_OK) rc = sync_and_check(c);
+    else (void)hipStreamSynchronize(c->s);
+    if (rc == MGP_OK && bad) {
+        int a = 0;
+        while (!(bad >> a & 1)) ++a;
+        rc = c->fail(MGP_ERR_ARG, "%s: coefficient not positive and finite: axis %d", what, a);
+    }
+    if (rc != MGP_OK) {
+        release();
+        return rc;
+    }
+    drop_graphs(c);
+    for (size_t l = 0; l < c->lev.size(); ++l) {
+        Level& L = c->lev[l];
+        vc_free(L);
+        for (int a = 0; a < 3; ++a) L.vb[a] = nw[l].vb[a];
+        L.vwx = nw[l].vwx, L.vwy = nw[l].vwy;
+    }
+    vc_engines(c, true);
+    return MGP_OK;
+}
+
+int mgp_clear_coefficients(mgp_ctx* c)
+{
+    if (!c) return MGP_ERR_ARG;
+    if (!c->vc) return MGP_OK;
+    TRY(sync_and_check(c));
+    drop_graphs(c);
+    for (auto& L : c->lev) vc_free(L);
+    vc_engines(c, false);
+    return ensure_rscratch(c, true);
+}
+
+int mgp_get_coefficients(const mgp_ctx* cc, int level, int axis, void* dst, int64_t count, int mem)
+{
+    mgp_ctx* c = const_cast<mgp_ctx*>(cc);
+    if (!c) return MGP_ERR_ARG;
+    const char* what = "mgp_get_coefficients";
+    if (!c->vc) return c->fail(MGP_ERR_STATE, "%s: no coefficients are set (mgp_set_coefficients)", what);
+    if (check_level(c, level) != MGP_OK || axis < 0 || axis >= c->o.dim || !dst)
+        return c->fail(MGP_ERR_ARG, "%s: bad level / axis / buffer", what);
+    if (mem != MGP_MEM_HOST && mem != MGP_MEM_DEVICE) return c->fail(MGP_ERR_ARG, "%s: unknown mem %d", what, mem);
+    const Level& L = c->lev[(size_t)level];
+    const int64_t n = (L.p.nx + (axis == 0)) * (L.p.ny + (axis == 1)) * (c->o.dim == 3 ? L.g.nz + (axis == 2) : 1);
+    if (count != n) return c->fail(MGP_ERR_ARG, "%s: count %lld, the array holds %lld", what, (long long)count, (long long)n);
+    char* dev = (char*)dst;
+    if (mem == MGP_MEM_HOST && hipMalloc(&dev, (size_t)n * c->rb) != hipSuccess) {
+        (void)hipGetLastError();
+        return c->fail(MGP_ERR_OOM, "%s: no room for the device copy", what);
+    }
+    int rc = MGP_OK;
+    if (mgp::launch_vc_unpack(c->rb, c->o.dim, axis, vc_of(c, L), dev, L.g, c->s) != hipSuccess ||
+        (mem == MGP_MEM_HOST && hipMemcpyAsync(dst, dev, (size_t)n * c->rb, hipMemcpyDeviceToHost, c->s) != hipSuccess))
+        rc = c->fail(MGP_ERR_HIP, "%s: launch or copy failed", what);
+    const int rs = sync_and_check(c);
+    if (mem == MGP_MEM_HOST) (void)hipFree(dev);
+    return rc != MGP_OK ? rc : rs;
+}
+
 // ---- mixed-precision defect correction (cpu.lua:196-216 with real = 'double', around the fp32 cycles) ----
 
 static int refine_active(mgp_ctx* c, const char* what)
@@ -3358,6 +3595,7 @@ int mgp_refine_begin(mgp_ctx* c)
         return c->fail(MGP_ERR_STATE, "mgp_refine_begin: one GPU only (not world > 1, a loopback or group rank "
                                       "context, or MGP_TRANSPORT=rccl)");
     if (c->refining()) return c->fail(MGP_ERR_STATE, "mgp_refine_begin: refinement is already active");
+    if (c->vc) return vc_refuses(c, "mgp_refine_begin");
     Level& L = c->lev[0];
     TRY(materialize_zero(c, L));
     TRY(sync_and_check(c));  // (nothing is in flight through the staging buffer, which may be replaced)
@@ -3578,6 +3816,7 @@ int mgp_cg_solve(mgp_ctx* c, double epsilon, int32_t maxiter, void* x_out, int m
 {
     if (!c || maxiter < 0) return MGP_ERR_ARG;
     if (c->refining()) return refine_refuses(c, "mgp_cg_solve");
+    if (c->vc) return vc_refuses(c, "mgp_cg_solve");
     if (c->o.world > 1) return c->fail(MGP_ERR_STATE, "mgp_cg_solve: single-GPU contexts only");
     Level& L = c->lev[0];
     const size_t bytes = (size_t)L.alloc * c->rb;

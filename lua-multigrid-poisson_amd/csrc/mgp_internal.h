@@ -1,7 +1,7 @@
 // mgp_internal.h — shared declarations between the C-ABI layer (mgp_api.cpp) and the CDNA4 kernel units:
 // mgp_kernels.hip (one launch per piece; k_zs's stage-split variants and the 2D k_ys), mgp_zs.hip / mgp_zs_f64.hip (k_zs, the fused
 // phases' planning and dispatch), mgp_tail.hip (coarse tail), mgp_blk.hip / mgp_blk2.hip (tiled phases), mgp_gslex.hip,
-// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip, mgp_fmg.hip, mgp_project.hip.  The last block holds what the kernel units
+// mgp_fw.hip, mgp_bres.hip, mgp_refine.hip, mgp_batch.hip, mgp_krylov.hip, mgp_mean.hip, mgp_fmg.hip, mgp_project.hip, mgp_vc.hip.  The last block holds what the kernel units
 // call in each other.  Not part of the public ABI (include/mgpoisson.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,6 +54,7 @@ struct PieceTuning {
     // MGP_RR_SCALAR_CELLS: residual + restriction below this many coarse cells runs one thread per coarse cell
     // (k_resrestrict_s) instead of one 16-byte vector of them along x (k_resrestrict<T, D>)
     int64_t rr_scalar_cells = (int64_t)1 << 22;
+    bool rr_scalar_env = false;  // MGP_RR_SCALAR_CELLS was given (the coefficient path's 16-byte form runs only then)
     // MGP_RR_PAIR_CELLS: from this many coarse cells up to rr_scalar_cells, fp32 runs two coarse cells per thread
     // (k_resrestrict<T, D, 2>); -1: the default rule, 2D from 2^18 and 3D never
     int64_t rr_pair_cells = -1;
@@ -228,6 +229,39 @@ hipError_t launch_divergence_batch(int rb, int dim, const void* vx, const void* 
                                    hipStream_t s);
 hipError_t launch_gradient_batch(int rb, int dim, bool subtract, const void* u, void* vx, void* vy, void* vz, Geo g, double cl,
                                  int nm, hipStream_t s);
+
+// The variable-coefficient operator A_beta u = div(beta grad u) (mgp_vc.hip; mgp_set_coefficients in
+// include/mgpoisson.h has the definition).  rb = 4 / 8, one rank's whole box.  A level's coefficients: b[axis] = interior
+// plane 0 of an array in the level's packed layout (ghost planes as u has them) that holds each cell's LOWER face of
+// that axis, the faces z = nz in its upper ghost plane; wx = the faces x = nx as [k][j] (ny nz reals); wy = the faces
+// y = ny as [k][i & 1][i >> 1] (2 hw nz reals).  b[2] is not touched in 2D.
+struct VcCoef {
+    void* b[3];
+    void* wx;
+    void* wy;
+};
+// bad |= bit when one of p[0, n) is not finite and > 0
+hipError_t launch_vc_check(int rb, const void* p, int64_t n, int* bad, int bit, hipStream_t s);
+// lex: the faces of `axis` in mgp_divergence's lexicographic layout (device memory)
+hipError_t launch_vc_pack(int rb, int dim, int axis, const void* lex, VcCoef vc, Geo g, hipStream_t s);
+hipError_t launch_vc_unpack(int rb, int dim, int axis, VcCoef vc, void* lex, Geo g, hipStream_t s);
+// the coarse level's (gc) faces of `axis`: the mean of the 2^(d-1) fine faces that tile each
+hipError_t launch_vc_coarsen(int rb, int dim, int axis, VcCoef fine, Geo g, VcCoef coarse, Geo gc, hipStream_t s);
+// The pieces, as launch_half_sweep / launch_residual_restrict / launch_residual_field / launch_residual_norm /
+// launch_gradient define them, on A_beta.  The half-sweep's err partials: half_blocks_vc() per colour; the norm's
+// scratch: 2 * (resnorm_blocks_vc() + sum_scratch(resnorm_blocks_vc())) doubles.
+int half_blocks_vc(int rb, Geo g);
+hipError_t launch_half_sweep_vc(int rb, int dim, int color, const void* other, const void* f, void* dst, const void* old,
+                                double* partials, Geo g, double h, double cl, VcCoef vc, hipStream_t s);
+hipError_t launch_residual_restrict_vc(int rb, int dim, const void* u, const void* f, void* R, Geo g, Geo gc, double h,
+                                       double cl, VcCoef vc, const PieceTuning& pt, hipStream_t s);
+hipError_t launch_residual_field_vc(int rb, int dim, const void* u, const void* f, void* r, Geo g, double h, double cl,
+                                    VcCoef vc, hipStream_t s);
+int resnorm_blocks_vc(Geo g);
+hipError_t launch_residual_norm_vc(int rb, int dim, const void* u, const void* f, Geo g, double h, double cl, VcCoef vc,
+                                   double* partials, double* out, hipStream_t s);
+hipError_t launch_gradient_vc(int rb, int dim, bool subtract, const void* u, void* vx, void* vy, void* vz, Geo g,
+                              double cl, VcCoef vc, hipStream_t s);
 
 // Temporally blocked smoothing phases of a replicated 3D red/black level (ns = 2 sweeps):
 //   pre : dst = nu1 sweeps of src; R (coarse packed, Geo gc) = restrict(residual(dst))

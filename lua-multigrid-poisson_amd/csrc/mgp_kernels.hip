@@ -2757,7 +2757,7 @@ static void half_f32d(bool err, unsigned nb, int color, const void* other, const
 PieceTuning piece_tuning_from_env()
 {
     PieceTuning t;
-    if (const char* v = std::getenv("MGP_RR_SCALAR_CELLS")) t.rr_scalar_cells = std::atoll(v);
+    if (const char* v = std::getenv("MGP_RR_SCALAR_CELLS")) t.rr_scalar_cells = std::atoll(v), t.rr_scalar_env = true;
     if (const char* v = std::getenv("MGP_RR_PAIR_CELLS")) t.rr_pair_cells = std::atoll(v);
     if (const char* v = std::getenv("MGP_BRES_VN")) t.bres_vn = std::atoi(v);
     if (const char* v = std::getenv("MGP_NT")) t.nt = std::atoi(v) != 0;

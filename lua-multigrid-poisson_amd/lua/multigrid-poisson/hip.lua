@@ -107,6 +107,10 @@ int         mgp_fmg(mgp_ctx* c, int32_t cycles_per_level, int32_t final_cycles, 
 int         mgp_divergence(mgp_ctx* c, const void* vx, const void* vy, const void* vz, int mem);
 int         mgp_gradient(mgp_ctx* c, int op, void* vx, void* vy, void* vz, int mem);
 int         mgp_project(mgp_ctx* c, void* vx, void* vy, void* vz, int mem, int32_t fmg_cycles, int32_t cycles, double norms[2]);
+int         mgp_set_coefficients(mgp_ctx* c, const void* bx, const void* by, const void* bz, int mem);
+int         mgp_clear_coefficients(mgp_ctx* c);
+int         mgp_has_coefficients(const mgp_ctx* c);
+int         mgp_get_coefficients(const mgp_ctx* c, int level, int axis, void* dst, int64_t count, int mem);
 int         mgp_refine_remove_mean(mgp_ctx* c, int which, double* mean);
 int         mgp_group_remove_mean(mgp_group* g, int level, int which, double* mean);
 int         mgp_batch_remove_mean(mgp_batch* b, int level, int which, double* means);
@@ -576,6 +580,29 @@ function MultigridHIP:project(vx, vy, vz, fmg, cycles)
 	local norms = ffi.new('double[2]')
 	check(lib.mgp_project(ctx, vx, vy, vz, 0, fmg or 1, cycles or 1, norms), ctx)
 	return norms[0], norms[1]
+end
+
+-- Variable coefficients (this build's addition; include/mgpoisson.h has the definition): div(beta grad psi) = f with
+-- positive face coefficients bx, by[, bz], host buffers laid out like the projection's faces (mg:faceCounts()).
+function MultigridHIP:setCoefficients(bx, by, bz)
+	local ctx = projectionCtx(self, 'setCoefficients')
+	check(lib.mgp_set_coefficients(ctx, bx, by, bz, 0), ctx)
+end
+
+function MultigridHIP:clearCoefficients()
+	local ctx = projectionCtx(self, 'clearCoefficients')
+	check(lib.mgp_clear_coefficients(ctx), ctx)
+end
+
+function MultigridHIP:hasCoefficients()
+	return lib.mgp_has_coefficients(projectionCtx(self, 'hasCoefficients')) == 1
+end
+
+-- level `level`'s faces of `axis` (0 x, 1 y, 2 z) into dst (count reals of the solver's real type)
+function MultigridHIP:getCoefficients(level, axis, dst, count)
+	local ctx = projectionCtx(self, 'getCoefficients')
+	check(lib.mgp_get_coefficients(ctx, level, axis, dst, count, 0), ctx)
+	return dst
 end
 
 -- cpu-raw.lua:239-258 / gpu.lua:348-373: two outer iterations

@@ -125,6 +125,10 @@ SIGNATURES = {
     "mgp_divergence": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int]),
     "mgp_gradient": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]),
     "mgp_project": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _i32, _i32, _P(_dbl)]),
+    "mgp_set_coefficients": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int]),
+    "mgp_clear_coefficients": (ctypes.c_int, [_vp]),
+    "mgp_has_coefficients": (ctypes.c_int, [_vp]),
+    "mgp_get_coefficients": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _i64, ctypes.c_int]),
     "mgp_sync": (ctypes.c_int, [_vp]),
     "mgp_metrics": (ctypes.c_int, [_vp, _P(_dbl), _P(_i64), _P(_dbl)]),
     "mgp_set_coarse_level": (ctypes.c_int, [_vp, _i64]),

@@ -289,6 +289,34 @@ class Context:
         self._chk(L.lib.mgp_project(self._h, vx_ptr, vy_ptr, vz_ptr, mem, int(fmg), int(cycles), out))
         return (out[0], out[1]) if norms else None
 
+    # -- face coefficients: div(beta grad psi) = f (mgp_set_coefficients; include/mgpoisson.h has the definition) --
+    def set_coefficients(self, bx, by, bz=None):
+        """Positive face coefficients beta of level 0 (host arrays shaped like the projection's faces, see face_shapes).
+        Until clear_coefficients the cycle, the pieces, the norms and the projection use div(beta grad u)."""
+        self._chk(L.lib.mgp_set_coefficients(self._h, *self._face_ptrs(self._faces(bx, by, bz, False)), L.MEM_HOST))
+        self._read_levels()
+
+    def set_coefficients_ptr(self, bx_ptr: int, by_ptr: int, bz_ptr: "int | None" = None, mem=L.MEM_DEVICE):
+        self._chk(L.lib.mgp_set_coefficients(self._h, bx_ptr, by_ptr, bz_ptr, mem))
+        self._read_levels()
+
+    def clear_coefficients(self):
+        """Back to the constant-coefficient engines (and their bits)."""
+        self._chk(L.lib.mgp_clear_coefficients(self._h))
+        self._read_levels()
+
+    def has_coefficients(self) -> bool:
+        return bool(self._chk(L.lib.mgp_has_coefficients(self._h)))
+
+    def get_coefficients(self, level: int, axis: int):
+        """The face coefficients of `axis` (0 x, 1 y, 2 z) on `level`, shaped (nz, ny, nx) with + 1 along the axis."""
+        lv = self.levels[level]
+        shape = [lv["nz_local"] if self.opts.dim == 3 else 1, lv["ny"], lv["nx"]]
+        shape[2 - int(axis)] += 1
+        out = np.empty(shape, dtype=self.dtype)
+        self._chk(L.lib.mgp_get_coefficients(self._h, int(level), int(axis), out.ctypes.data, out.size, L.MEM_HOST))
+        return out
+
     def set_coarse_level(self, size: int):
         """Levels of nx <= size run in the one-launch LDS coarse engine (cpuDepth, cpu-gpu.lua:61)."""
         self._chk(L.lib.mgp_set_coarse_level(self._h, int(size)))

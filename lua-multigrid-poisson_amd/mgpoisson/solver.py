@@ -314,6 +314,15 @@ class MultigridHIP(_RawFields):
         (div_before, div_after), the 2-norms of D v before and after."""
         return self._projection_ctx("project").project(vx, vy, vz, fmg, cycles)
 
+    def setCoefficients(self, bx, by, bz=None):
+        """Solve div(beta grad psi) = f from here on (this build's addition, mgp_set_coefficients): positive face
+        coefficients as host arrays shaped like the projection's faces.  ``clearCoefficients`` returns to the
+        constant-coefficient Laplacian."""
+        self._projection_ctx("setCoefficients").set_coefficients(bx, by, bz)
+
+    def clearCoefficients(self):
+        self._projection_ctx("clearCoefficients").clear_coefficients()
+
     def twoGrid(self, h, u, f):
         """cpu.lua:70 twoGrid(h, u, f): u updated in place.  u / f are (L, L[, L]) host arrays, or
         cpu.lua-style 1-based-indexed nested lists u[i][j] (x = i), whose rows are updated in place."""
